@@ -4,13 +4,28 @@
 One "step" = one pass of the hot path (nipamd_fb: forward_backward_inference,
 src/nip.c:1320, batched) over one batch of B synthetic sequences x T time
 slices resident in HBM -- SURVEY 8(d) config 2: HMM-shaped DBN with 16 hidden
-and 16 observed states, B = 4096 sequences per GPU, T = 1024.  The same JSON
-line carries a `secondary` object with SURVEY 8(d)'s other GPU configs timed
-the same way in the same run: config 3 (demo1 @ 32 states, 65536 x 256),
-config 4 (one em_learn iteration over the 131072 x 1024 per-GPU shard) and
-config 5 (the 64^4 wide clique, 256 x 128).
+and 16 observed states, B = 4096 sequences per GPU, T = 1024.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--no-secondary]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W]
+                  [--dump-outputs DIR] [--full [--no-secondary] [--no-cpu-baseline]]
+
+A plain run does what the headline figure needs and no more: it sets the
+workload up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the JSON line (its roofline fields are
+arithmetic on the same timed steps and the committed PMC pass).
+
+--full adds everything that takes runs of its own: the CPU baselines (a child
+process, before this one touches the GPU), the PCIe-inclusive call, config
+5's fold timing, the detail file (--detail) and, under `secondary` in the
+same JSON line, SURVEY 8(d)'s other GPU configs timed the same way: config 3
+(demo1 @ 32 states, 65536 x 256), config 4 (one em_learn iteration over the
+131072 x 1024 per-GPU shard) and config 5 (the 64^4 wide clique, 256 x 128).
+
+--dump-outputs DIR writes what a caller of the timed path holds after the last
+timed step (fb: posterior, loglik, status) as DIR/<name>.npy, float32 or
+float64.  The inputs are seeded, so two runs with the same arguments see the
+same inputs.  An array that does not fit its share of DUMP_BUDGET is cut to a
+fixed, seeded sample of its rows (DUMP_SEED; the same rows in every run).
 
 N > 1: one process per GPU.  Run directly with --gpus N, bench.py starts
 ``python -m torch.distributed.run --nproc-per-node N`` on itself as a child
@@ -327,9 +342,40 @@ def row64_issue_roof(B: int, T: int, kern_ms: float):
             "source": "profiles/r04/isa_row64_step.json, profiles/r04/gpu/r04h_mb_r64.txt"}
 
 
-def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0):
+DUMP_BUDGET = 48 << 20    # bytes --dump-outputs writes in all (every rank's files together)
+DUMP_SEED = 20260101      # seeds the row sample of an array larger than its share
+
+
+def dump_outputs(dirname, arrays, world, rank):
+    """Write {name: tensor or ndarray} as dirname/<name>.npy (rank r > 0:
+    <name>.rank<r>.npy), float32 or float64.  Every array has an equal share
+    of DUMP_BUDGET; a larger one is cut to a sorted, seeded sample of its rows
+    (of its elements, when one row is already too large), gathered on the
+    device so that only the sample crosses to the host."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // world // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        item = 4 if a.dtype in (torch.float32, torch.float16, torch.bfloat16) else 8
+        if a.numel() * item > share:
+            rng = np.random.default_rng(DUMP_SEED)
+            row = a[0].numel() * item if a.dim() >= 2 else share + 1
+            if row > share:
+                a, row = a.reshape(-1), item
+            idx = np.sort(rng.choice(a.shape[0], share // row, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        out = a.detach().cpu().numpy()
+        out = out.astype(np.float32 if item == 4 else np.float64)
+        np.save(os.path.join(dirname, name + (".rank%d" % rank if rank else "") + ".npy"), out)
+
+
+def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0, full=False, dump_dir=None):
     """Time `steps` steps of one workload (barrier + synchronize on both sides,
-    max over ranks) and build its record."""
+    max over ranks) and build its record.  full: also the measurements that
+    take runs of their own (PCIe-inclusive call, config 5's fold).  dump_dir:
+    write the last timed step's outputs there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     import nip_amd
@@ -357,6 +403,9 @@ def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0):
 
         def step():
             nip_amd.generate_data(model, 12345 + rank, B, T, sample)
+
+        def outputs():
+            return {"sample": sample}
     elif name == "em":
         from nip_amd import em as nem
         group = dist.group.WORLD if world > 1 else None
@@ -370,16 +419,25 @@ def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0):
             em_state["params"] = p
             em_state["ll"].append(l)
             em_state["exchange_ms"].append(tm.get("exchange_ms", 0.0))
+
+        def outputs():
+            return {"params": em_state["params"], "loglik": np.asarray(em_state["ll"][-1:], dtype=np.float64)}
     elif name not in ESTEP_WORKLOADS:
         post = torch.empty((B, T, N), dtype=torch.float64, device=dev)
 
         def step():
             nip_amd.forward_backward_inference(model, obs, ov, [q], post, ll, st)
+
+        def outputs():
+            return {"posterior": post, "loglik": ll, "status": st}
     else:
         counts = torch.ones((model.param_size(),), dtype=torch.float64, device=dev)
 
         def step():
             nip_amd.e_step(model, obs, ov, counts, ll, st)
+
+        def outputs():
+            return {"counts": counts, "loglik": ll, "status": st}
 
     def barrier():
         if world > 1:
@@ -439,6 +497,8 @@ def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0):
         t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms = float(t[0]), float(t[1])
+    if dump_dir:
+        dump_outputs(dump_dir, outputs(), world, rank)
 
     units = B * T * steps * world
     value = units / elapsed
@@ -634,7 +694,7 @@ def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0):
                       "observed_states": M, "observed_vars": len(ov), "parallelism": "dp%d" % world},
            "roofline": roof}
     rec.update(extra)
-    if rank == 0 and world == 1 and name in ("fb", "config3", "config5") and headline:
+    if full and rank == 0 and world == 1 and name in ("fb", "config3", "config5") and headline:
         # PCIe-inclusive figure: the same batch from host buffers
         # through nipamd_fb_host (H2D obs, kernels, D2H posteriors)
         host_obs = np.ascontiguousarray(obs_np)
@@ -644,7 +704,7 @@ def run_workload(name, args, world, rank, dev, steps, warmup, min_warm_s=0.0):
         el1 = time.perf_counter() - t1
         rec["pcie_inclusive"] = {"value": B * T / el1, "unit": "sequence-timesteps/s", "ms": el1 * 1e3,
                                  "note": "host buffers in and out (pageable), one call; not the headline"}
-    if name == "config5":
+    if full and name == "config5":
         # the in-clique marginalisation: 64^4 entries summed over the hidden
         # parents on the GPU (fold.hip), once per model version
         fms, fby = [], 0.0
@@ -727,38 +787,52 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="timed steps of the headline (0: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baselines, the secondary "
+                         "configs (workload fb), the PCIe-inclusive call, config 5's fold timing and the "
+                         "detail file; --no-secondary and --no-cpu-baseline take their part out again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the outputs of the last timed step of the headline workload as DIR/<name>.npy "
+                         "(float32 or float64, a seeded row sample of an array over its share of 48 MB); "
+                         "for the workloads whose output depends on how many steps ran (em, e_step) the "
+                         "time-based extra warmup is off, as with --min-warm 0")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="sequences per GPU (0: the workload's)")
     ap.add_argument("--T", type=int, default=0, help="time slices (0: the workload's)")
     ap.add_argument("--N", type=int, default=16)
     ap.add_argument("--M", type=int, default=16)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="fb",
-                    help="fb: the headline metric (config 2 smoothing) plus the secondary configs; "
+                    help="fb: the headline metric (config 2 smoothing), with --full plus the secondary configs; "
                          "estep: one batched e_step (config 4 per-GPU shard); em: config 4, one step = "
                          "one em_learn iteration (m_step, e_step of the shard, the packed all-gather "
                          "over RCCL, finalize); config3: demo1 @ 32 states smoothing; config5: wide-"
                          "clique smoothing; jtree: a factorial HMM on the general join-tree engine; "
                          "joint: the same slice as a joint-interface chain; generate: generate_data")
-    ap.add_argument("--no-secondary", action="store_true", help="the headline workload only")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: the headline workload only")
     ap.add_argument("--min-warm", type=float, default=0.5,
                     help="after the W warmup steps, add untimed steps (at most 64) until this many seconds "
                          "of warmup ran, as the secondary lines do: the f64 kernels run their first "
                          "launches at a lower clock (config 2: 0.278-0.288 ms per step after 3 warmup "
                          "steps, 0.243-0.252 after 0.5 s, profiles/r05/gpu/r05av_warm.txt); 0 = exactly W. "
                          "The line's 'warmup' is the count that ran, 'warmup_requested' W")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=8.0, help="seconds per CPU baseline")
     ap.add_argument("--no-check", action="store_true", help="skip the output sanity check (ablation builds)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="the full records (notes, byte breakdowns, roof sources) as JSON ('' = none)")
+                    help="with --full: the full records (notes, byte breakdowns, roof sources) as JSON "
+                         "('' = none)")
     args = ap.parse_args()
     world = launch_or_check(args, sys.argv[1:])
     rank = int(os.environ.get("RANK", "0"))
-    secondary = [] if (args.no_secondary or args.workload != "fb" or args.batch or args.T) else SECONDARY
+    if args.steps < 0 or args.warmup < 0:
+        sys.exit("bench: --steps and --warmup must not be negative")
+    secondary = SECONDARY if args.full and not (args.no_secondary or args.workload != "fb" or args.batch
+                                                or args.T) else []
+    cpu_base = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
 
     # CPU baselines first, in a child process, while nothing here has touched the GPU
     cpu = {}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and args.workload != "generate":
+    if cpu_base and args.workload != "generate":
         cpu = cpu_baselines([args.workload] + secondary, args.cpu_budget)
 
     import torch
@@ -772,26 +846,31 @@ def main():
     torch.cuda.set_device(dev)
 
     steps = args.steps or WORKLOADS[args.workload][6]
-    rec = run_workload(args.workload, args, world, rank, dev, steps, args.warmup, min_warm_s=args.min_warm)
+    min_warm = args.min_warm
+    if args.dump_outputs and args.workload in ESTEP_WORKLOADS + ("em",):
+        min_warm = 0.0      # the dumped counts / parameters depend on the number of steps run: keep it fixed
+    rec = run_workload(args.workload, args, world, rank, dev, steps, args.warmup, min_warm_s=min_warm,
+                       full=args.full, dump_dir=args.dump_outputs)
     if args.workload in cpu:
         rec["cpu_baseline"] = cpu[args.workload]
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and args.workload == "generate":
+    if cpu_base and args.workload == "generate":
         rec["cpu_baseline"] = cpu_baseline_generate(*WORKLOADS["generate"][1](args), T=rec["config"]["T"])
     line = compact(rec)
     detail = {"headline": rec}
     if secondary:
-        sec, full = {}, {}
+        sec, sec_full = {}, {}
         for w in secondary:
-            r = run_workload(w, args, world, rank, dev, WORKLOADS[w][6], 2 if w != "em" else 1, min_warm_s=0.5)
+            r = run_workload(w, args, world, rank, dev, WORKLOADS[w][6], 2 if w != "em" else 1, min_warm_s=0.5,
+                             full=True)
             if w in cpu:
                 r["cpu_baseline"] = cpu[w]
             key = WORKLOADS[w][0] if w != "estep_config3" else "config3_estep"
-            full[key] = r
+            sec_full[key] = r
             sec[key] = compact(r, secondary=True)
         line["secondary"] = sec
-        detail["secondary"] = full
+        detail["secondary"] = sec_full
     if rank == 0:
-        if args.detail:
+        if args.full and args.detail:
             try:
                 os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
                 with open(args.detail, "w") as f:
