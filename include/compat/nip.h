@@ -130,6 +130,13 @@ uncertain_series forward_inference(time_series ts, nip_variable vars[], int nvar
                                    double* loglikelihood);
 uncertain_series forward_backward_inference(time_series ts, nip_variable vars[], int nvars,
                                             double* loglikelihood);
+/* the most likely state sequence of vars (the model's interface, all of it)
+ * given ts: Viterbi on the GPU (nipamd_mlss).  The reference declares this
+ * (nip.h:431-438) and returns NIP_ERROR_GENERAL from an unfinished body
+ * (nip.c:1620-1699).  A time series over vars, freed with free_timeseries;
+ * NULL (after nip_report_error) for a request outside the engine's scope, or
+ * with NIP_ERROR_BAD_LUCK for evidence without probability mass. */
+time_series mlss(nip_variable vars[], int nvars, time_series ts);
 int em_learn(time_series* ts, int n_ts, double threshold, nip_double_list learning_curve);
 
 /* sampled on the GPU from the caller's rand() stream (nip.c:2325-2478) */

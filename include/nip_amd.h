@@ -469,6 +469,58 @@ int nipamd_likelihood_host(nipamd_model* m, const int32_t* obs, int n_obs, const
 int nipamd_hugin_passes(int n_tables, double* const* tables, const int* ndim, const int* card,
                         int n_passes, const int* passes, const int* maps);
 
+/*
+ * Batched mlss(): the most likely state sequence, "the Viterbi algorithm,
+ * Max-Sum inference" the reference declares (src/nip.h:431-438) and leaves
+ * unimplemented (src/nip.c:1620-1699 ends in NIP_ERROR_GENERAL).  B
+ * independent sequences of equal length T, asynchronous on `stream`.
+ *
+ * Scope: models with an interface-chain plan; the variables of interest are
+ * exactly the interface -- the one interface variable of the slice, or every
+ * variable of a joint interface, each once, in any order.  For that choice
+ * the rest of the slice (hidden parents under their priors, leaf children,
+ * the slice -1 copy) sums out of every step, and the marginal MAP of the
+ * interface sequence is an exact Viterbi recursion over the plan's tables
+ * (A the folded transition, pi the prior of slice -1, e_t the evidence of
+ * step t: observed children's rows, row sums for missing values, zero for a
+ * state out of range):
+ *
+ *   delta_0[y] = (sum_x pi[x] A[x][y]) e_0[y]
+ *   delta_t[y] = (max_x delta_{t-1}[x] A[x][y]) e_t[y]     psi_t[y] = the LOWEST x attaining the max
+ *   x*_{T-1}   = the LOWEST y attaining max_y delta_{T-1}[y];  x*_{t-1} = psi_t[x*_t]
+ *
+ * in fp64, the probability domain, rescaled by exact powers of two (which
+ * change no comparison) whose exponents are carried into logp.
+ *
+ *   d_obs     int32 [B][T][n_obs]; state index, <0 = missing; at most four
+ *             columns, each the interface variable or a leaf child of it
+ *   query     host int[n_query]: the interface variable(s)
+ *   d_path    int32 [B][T][n_query]: the state of query[j] at step t
+ *   d_logp    double [B] ln max_y delta_{T-1}[y] -- ln P(path, evidence) for
+ *             a proper model, else the log of the tables' unnormalised measure
+ *             (as d_ll of nipamd_fb) -- or NULL
+ *   d_status  uint32 [B] or NULL.  A sequence whose evidence leaves no mass at
+ *             some step gets NIPAMD_STATUS_ZERO_MASS, logp = -DBL_MAX and -1
+ *             in every path entry; the other sequences are unaffected.
+ *
+ * NULL m / d_obs (with n_obs > 0) / d_path: NIP_ERROR_NULLPOINTER.  B <= 0,
+ * T <= 0 or a variable index out of range: NIP_ERROR_INVALID_ARGUMENT.
+ * Everything outside the scope -- no chain plan, NIPAMD_ENGINE_JTREE, a query
+ * that is not exactly the interface, evidence the chain plan does not route,
+ * more than four observed columns -- is NIPAMD_ERROR_UNSUPPORTED, decided on
+ * the host before anything is queued; nipamd_last_error() names the condition.
+ */
+int nipamd_mlss(nipamd_model* m, const int32_t* d_obs, int n_obs,
+                const int* obs_vars, int B, int T, int n_query,
+                const int* query, int32_t* d_path, double* d_logp,
+                uint32_t* d_status, void* stream);
+
+/* Host-buffer form of nipamd_mlss (copies in and out and synchronises). */
+int nipamd_mlss_host(nipamd_model* m, const int32_t* obs, int n_obs,
+                     const int* obs_vars, int B, int T, int n_query,
+                     const int* query, int32_t* path, double* logp,
+                     uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from . import build as _build
 
 __all__ = ["NipError", "Model", "parse_model", "lib", "forward_backward_inference",
            "forward_backward_inference_host", "forward_inference", "forward_inference_host",
+           "most_likely_states", "most_likely_states_host",
            "e_step", "estep_partial", "estep_finalize", "em_learn", "read_timeseries",
            "write_uncertainseries", "write_model", "em_learn_series", "LIB_PATH"]
 
@@ -62,6 +63,7 @@ EXPORTS = [
     "nipamd_model_set_engine", "nipamd_jt_plan_dump", "nipamd_hugin_passes",
     "nipamd_model_num_cliques", "nipamd_model_num_sepsets", "nipamd_model_clique",
     "nipamd_model_sepset", "nipamd_model_interface_cliques", "nipamd_model_set_tables", "nipamd_model_fold",
+    "nipamd_mlss", "nipamd_mlss_host",
 ]
 
 
@@ -100,6 +102,8 @@ def lib():
                                      vp, vp, vp]
         L.nipamd_filter.argtypes = L.nipamd_fb.argtypes
         L.nipamd_filter_host.argtypes = L.nipamd_fb_host.argtypes
+        L.nipamd_mlss.argtypes = L.nipamd_fb.argtypes
+        L.nipamd_mlss_host.argtypes = L.nipamd_fb_host.argtypes
         L.nipamd_estep.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_int, vp, vp, vp, vp]
         L.nipamd_estep_partial_size.argtypes = [vp]
         if hasattr(L, "nipamd_estep_partial_size_req"):      # (absent from A/B builds of older revisions)
@@ -403,6 +407,51 @@ def forward_backward_inference_host(model: Model, obs, obs_vars, query):
 def forward_inference_host(model: Model, obs, obs_vars, query):
     """forward_inference from host numpy buffers (PCIe-inclusive, synchronous)."""
     return _run_host(lib().nipamd_filter_host, model, obs, obs_vars, query)
+
+
+def most_likely_states(model: Model, obs, obs_vars, query, path=None, logp=None, status=None,
+                       stream=None):
+    """Batched mlss() (declared in src/nip.h:431-438, never implemented in the
+    reference): the most likely sequence of the interface given the evidence
+    (Viterbi), on the GPU.
+
+    obs: torch int32 CUDA tensor [B, T, n_obs] (state index, <0 missing);
+    query: the model's interface variable(s), all of them.  Returns
+    (path [B, T, len(query)] int32, logp [B] float64, status [B] int32), CUDA
+    tensors, computed asynchronously on ``stream`` (default: torch's current
+    stream).  A sequence without mass has status STATUS_ZERO_MASS, logp
+    -DBL_MAX and a path of -1.
+    """
+    import torch
+    if obs.dim() == 2:
+        obs = obs.unsqueeze(-1)
+    assert obs.dtype == torch.int32 and obs.is_cuda and obs.is_contiguous()
+    B, T, nobs = obs.shape
+    assert nobs == len(obs_vars)
+    dev = obs.device
+    path = _out_buf(path, (B, T, len(query)), torch.int32, dev, "path")
+    logp = _out_buf(logp, (B,), torch.float64, dev, "logp")
+    status = _out_buf(status, (B,), torch.int32, dev, "status")
+    _check(lib().nipamd_mlss(model._h, C.c_void_p(obs.data_ptr()), nobs, _ints(obs_vars), B, T,
+                             len(query), _ints(query), C.c_void_p(path.data_ptr()),
+                             C.c_void_p(logp.data_ptr()), C.c_void_p(status.data_ptr()),
+                             _stream_ptr(stream)))
+    return path, logp, status
+
+
+def most_likely_states_host(model: Model, obs, obs_vars, query):
+    """most_likely_states from host numpy buffers (PCIe-inclusive, synchronous)."""
+    obs = np.ascontiguousarray(np.asarray(obs, np.int32))
+    if obs.ndim == 2:
+        obs = obs[:, :, None]
+    B, T, nobs = obs.shape
+    path = np.zeros((B, T, len(query)), np.int32)
+    logp = np.zeros(B)
+    status = np.zeros(B, np.uint32)
+    _check(lib().nipamd_mlss_host(model._h, obs.ctypes.data_as(C.c_void_p), nobs, _ints(obs_vars),
+                                  B, T, len(query), _ints(query), path.ctypes.data_as(C.c_void_p),
+                                  logp.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+    return path, logp, status
 
 
 def generate_order(model: Model):

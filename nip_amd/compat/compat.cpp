@@ -10,6 +10,7 @@
 // compiled model.  Work goes to the GPU:
 //   forward_inference           -> nipamd_filter_host   (nip.c:1103-1315)
 //   forward_backward_inference  -> nipamd_fb_host       (nip.c:1320-1581)
+//   mlss                        -> nipamd_mlss_host     (nip.h:431-438)
 //   em_learn                    -> nipamd_em_learn      (nip.c:2076-2243)
 //   make_consistent             -> nipamd_hugin_passes  (nip.c:1600-1617)
 // with the evidence of MARKED observed variables only (insert_ts_step with
@@ -704,6 +705,89 @@ int forward_backward_inference_batch(time_series* ts, int n_ts, nip_variable var
   const int e = run_inference(ts, n_ts, vars, nvars, false, ucs_out, ll_out);
   if (e != NIP_NO_ERROR) engine_error(e);
   return e;
+}
+
+/* mlss (src/nip.h:431-438; the reference's body, src/nip.c:1620-1699, builds
+ * the result and stops at "NOT IMPLEMENTED YET"): the most likely states of
+ * vars -- the model's interface -- given the marked columns of ts, one
+ * nipamd_mlss_host call.  The result is a time series over the same model
+ * whose observed variables are vars and whose hidden ones are all the others
+ * in model order (the reference's prologue, nip.c:1632-1682); data[t][j] is
+ * the state of vars[j].  NULL after reporting the error for a request the
+ * engine does not take, and with NIP_ERROR_BAD_LUCK for evidence without mass. */
+time_series mlss(nip_variable vars[], int nvars, time_series ts) {
+  if (!ts || !vars || nvars < 1) {
+    REPORT(NIP_ERROR_INVALID_ARGUMENT);
+    return nullptr;
+  }
+  Compat* c = lookup(ts->model);
+  if (!c) {
+    REPORT(NIP_ERROR_INVALID_ARGUMENT);
+    return nullptr;
+  }
+  if (int e = sync_engine(c)) {
+    engine_error(e);
+    return nullptr;
+  }
+  std::vector<int> q(nvars), col, ov;
+  for (int i = 0; i < nvars; i++)
+    if ((q[i] = index_of(c, vars[i])) < 0) {
+      REPORT(NIP_ERROR_INVALID_ARGUMENT);
+      return nullptr;
+    }
+  marked_columns(ts, c, col, ov);
+  const int T = ts->length, k = (int)ov.size();
+  std::vector<int32_t> obs((size_t)(T > 0 ? T : 0) * (k > 0 ? k : 1) + 1, -1), path((size_t)(T > 0 ? T : 0) * nvars + 1);
+  for (int t = 0; t < T; t++)
+    for (int i = 0; i < k; i++) obs[(size_t)t * k + i] = ts->data[t][col[i]];
+  uint32_t st = 0;
+  int e;
+  {
+    RandGuard guard;
+    e = nipamd_mlss_host(c->eng, obs.data(), k, ov.data(), 1, T, nvars, q.data(), path.data(), nullptr, &st);
+  }
+  if (e != NIP_NO_ERROR) {
+    engine_error(e);
+    return nullptr;
+  }
+  if (st & NIPAMD_STATUS_ZERO_MASS) {
+    REPORT(NIP_ERROR_BAD_LUCK);
+    return nullptr;
+  }
+  const int nh = ts->model->num_of_vars - nvars;
+  auto* r = (time_series)std::calloc(1, sizeof(time_series_struct));
+  if (!r) {
+    REPORT(NIP_ERROR_OUTOFMEMORY);
+    return nullptr;
+  }
+  r->model = ts->model;
+  r->num_of_hidden = nh;
+  r->num_of_observed = nvars;
+  r->length = T;
+  r->hidden = (nip_variable*)std::calloc(nh > 0 ? nh : 1, sizeof(nip_variable));
+  r->observed = (nip_variable*)std::calloc(nvars, sizeof(nip_variable));
+  r->data = (int**)std::calloc(T, sizeof(int*));
+  bool ok = r->hidden && r->observed && r->data;
+  if (ok) {
+    std::memcpy(r->observed, vars, (size_t)nvars * sizeof(nip_variable));
+    int h = 0;
+    for (int i = 0; i < ts->model->num_of_vars && h < nh; i++) {
+      nip_variable v = ts->model->variables[i];
+      bool queried = false;
+      for (int j = 0; j < nvars; j++) queried |= vars[j] == v;
+      if (!queried) r->hidden[h++] = v;
+    }
+  }
+  for (int t = 0; ok && t < T; t++) {
+    ok = (r->data[t] = (int*)std::calloc(nvars, sizeof(int))) != nullptr;
+    for (int j = 0; ok && j < nvars; j++) r->data[t][j] = path[(size_t)t * nvars + j];
+  }
+  if (!ok) {
+    REPORT(NIP_ERROR_OUTOFMEMORY);
+    free_timeseries(r);
+    return nullptr;
+  }
+  return r;
 }
 
 int em_learn(time_series* ts, int n_ts, double threshold, nip_double_list learning_curve) {

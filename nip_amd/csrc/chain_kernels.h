@@ -209,6 +209,39 @@ struct DeriveArgs {
 };
 int derive_launch(const DeriveArgs& a, hipStream_t stream);
 
+// most likely interface state sequence (viterbi.hip, chain_viterbi_kernel):
+// every chain plan, N <= 64, up to four observed columns, the wide request
+// tables.  The path goes out as int32, one column per queried variable: digit
+// (state / qstride[j]) % qcard[j] of the interface state (a single interface
+// variable: one column, qstride 1, qcard N); -1 everywhere, logp = -DBL_MAX
+// and status 1 for a sequence without mass.
+constexpr int kViterbiMaxQuery = 8;
+struct ViterbiArgs {
+  const int* obs;        // int32 observations [B][T][n_obs]
+  long obs_bstride;      // elements between sequences
+  int obs_tstride;       // elements between time steps
+  int ncol;              // observed columns
+  int col[4];            // their columns in obs
+  int M[4];              // their cardinalities
+  const double* tab[4];  // [(M+2)][64] per column: E, then the row sums, then 0
+  const double* ebase;   // [64] product of the unobserved children's row sums
+  const double* A;       // [64][64]
+  const double* u0;      // [64] pi A
+  long B;
+  int T, N;
+  unsigned long long* bp;   // back-pointer scratch, chain_viterbi_scratch_bytes
+  int* path;             // [B][T][nq]
+  long path_bstride;     // elements between sequences
+  int path_tstride;      // elements between time steps
+  int nq;                // path columns
+  int qstride[kViterbiMaxQuery], qcard[kViterbiMaxQuery];
+  double* logp;          // [B] or nullptr
+  unsigned* status;      // [B] or nullptr
+};
+size_t chain_viterbi_scratch_bytes(int N, long B, int T);
+size_t chain_viterbi_lds_bytes(const ViterbiArgs& a);
+int chain_viterbi_launch(const ViterbiArgs& a, hipStream_t stream);
+
 // generate_data (generate.hip): one sampling step per variable, in sampling
 // order.  In the first slice the conditional row of step i starts at
 // tab[off0 + idx], idx = sum_c value(ctx[c]) * stride[c] (in elements) with

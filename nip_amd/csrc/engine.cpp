@@ -67,6 +67,7 @@ struct ReqTables {
   int mtab_rows = 0;
   int mtab_off[4] = {0, 0, 0, 0};
   double* wv = nullptr;           // [64] A s_all
+  double* u0 = nullptr;           // [64] pi A: the first slice's prediction (mlss, viterbi.hip)
   double* arena = nullptr;        // the pool buffer all of the above live in (one upload)
 };
 
@@ -371,6 +372,16 @@ int ensure_req_tables(nipamd_model* mm, const Route& r, ReqTables** out) {
     sg.add(&t.mtab, MT);
     sg.add(&t.wv, wv);
   }
+  // mlss only (chain_viterbi_kernel): slice -1 is summed out, not maximised (x
+  // ascending).  Built for every route so that the request's tables stay one
+  // upload and one cache entry; fb, filter and e_step never read these 64 doubles.
+  std::vector<double> u0(64, 0.0);
+  for (int y = 0; y < N; y++) {
+    double acc = 0.0;
+    for (int x = 0; x < N; x++) acc += P.pi64[x] * P.A64[(size_t)x * 64 + y];
+    u0[y] = acc;
+  }
+  sg.add(&t.u0, u0);
   if (int rc = sg.commit(d, &t.arena)) return rc;
   d->reqs.push_back(std::move(t));
   *out = &d->reqs.back();
@@ -1295,6 +1306,138 @@ int nipamd_filter_host(nipamd_model* mm, const int32_t* obs, int n_obs, const in
                        int B, int T, int n_query, const int* query, double* post,
                        double* ll, uint32_t* status) {
   return fb_host_impl(mm, obs, n_obs, obs_vars, B, T, n_query, query, post, ll, status, true);
+}
+
+// Sequences per chain_viterbi_kernel launch: the back-pointer scratch of a
+// launch stays within kMlssScratch (8 bytes per sequence and step at N <= 16:
+// a config-4 shard, 131072 x 1024, is one launch of exactly this size), and a
+// longer batch runs as consecutive launches over the same scratch.  A multiple
+// of 16, so every launch but the last fills its blocks.
+constexpr size_t kMlssScratch = (size_t)1 << 30;
+static long mlss_chunk(int N, int T) {
+  const size_t per16 = nipamd::chain_viterbi_scratch_bytes(N, 16, T);
+  const long c = (long)(kMlssScratch / per16) * 16;
+  return c < 16 ? 16 : c;
+}
+
+// mlss: the verdict on a request -- the arguments, then the scope -- decided on
+// the host before anything touches the device.  obs / path: the caller's
+// buffers (device or host), only tested for NULL.  Fills the query columns of a
+// and the evidence route.
+static int mlss_check(nipamd_model* mm, const void* obs, int n_obs, const int* obs_vars, int B, int T, int n_query,
+                      const int* query, const void* path, nipamd::ViterbiArgs& a, Route& r) {
+  if (!mm || !path || (n_obs > 0 && (!obs || !obs_vars)) || (n_query > 0 && !query))
+    return fail(NIP_ERROR_NULLPOINTER, "mlss: NULL model, observations, variables or path");
+  if (B <= 0 || T <= 0 || n_obs < 0 || n_query < 0) return fail(NIP_ERROR_INVALID_ARGUMENT, "mlss: bad arguments");
+  const int nv = (int)mm->m.vars.size();
+  for (int i = 0; i < n_obs; i++)
+    if (obs_vars[i] < 0 || obs_vars[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "mlss: bad observed variable");
+  for (int i = 0; i < n_query; i++)
+    if (query[i] < 0 || query[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "mlss: bad query variable");
+  const auto& P = mm->m.chain;
+  if (mm->engine == NIPAMD_ENGINE_JTREE)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the engine is set to NIPAMD_ENGINE_JTREE; the most likely state "
+                                          "sequence runs on the interface-chain plan only");
+  if (!P.valid)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: model slice is not an interface chain (no chain plan; see DESIGN.md)");
+  // the variables of interest are the interface, all of it and nothing else
+  bool is_if = true;
+  if (!P.joint) {
+    is_if = n_query == 1 && query[0] == P.v_cur;
+    a.nq = 1; a.qstride[0] = 1; a.qcard[0] = P.N;
+  } else {
+    if ((int)P.jcur.size() > nipamd::kViterbiMaxQuery)
+      return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the joint interface has " + std::to_string(P.jcur.size()) +
+                                                " variables; the path holds at most " +
+                                                std::to_string(nipamd::kViterbiMaxQuery) + " columns");
+    is_if = n_query == (int)P.jcur.size();
+    for (int j = 0; is_if && j < n_query; j++) {
+      int k = -1, stride = 1;
+      for (size_t i = 0; i < P.jcur.size(); i++) if (P.jcur[i] == query[j]) k = (int)i;
+      for (int i = 0; i < j; i++) is_if &= query[i] != query[j];
+      if (k < 0) { is_if = false; break; }
+      for (int i = 0; i < k; i++) stride *= mm->m.vars[P.jcur[i]].card;
+      a.qstride[j] = stride; a.qcard[j] = mm->m.vars[query[j]].card;
+    }
+    a.nq = n_query;
+  }
+  if (!is_if)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the query is not exactly the interface (every outgoing-interface "
+                                          "variable of the slice once, and no other variable)");
+  std::string why;
+  if (!route_request(mm, n_obs, obs_vars, 0, nullptr, r, why)) return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: " + why);
+  return 0;
+}
+
+// chain_viterbi_kernel over the chain plan's tables, asynchronous on stream
+static int mlss_impl(nipamd_model* mm, const int32_t* d_obs, int n_obs, const int* obs_vars, int B, int T,
+                     int n_query, const int* query, int32_t* d_path, double* d_logp, uint32_t* d_status,
+                     void* stream) {
+  nipamd::ViterbiArgs a{};
+  Route r;
+  if (int rc = mlss_check(mm, d_obs, n_obs, obs_vars, B, T, n_query, query, d_path, a, r)) return rc;
+  const auto& P = mm->m.chain;
+  if (int rc = ensure_tables(mm)) return rc;           // (the GPU fold of a fold_gpu plan included)
+  ReqTables* rt = nullptr;
+  if (int rc = ensure_req_tables(mm, r, &rt)) return rc;
+  const int N = P.N;
+  const long chunk = mlss_chunk(N, T);
+  if (int rc = ensure_scratch(mm, nipamd::chain_viterbi_scratch_bytes(N, B < chunk ? B : chunk, T))) return rc;
+  DevState* d = dev_of(mm);
+  const long ocols = n_obs > 0 ? n_obs : 1;
+  a.obs_bstride = (long)T * ocols; a.obs_tstride = (int)ocols;
+  a.ncol = r.ncol;
+  for (int c = 0; c < r.ncol; c++) {
+    a.col[c] = r.col[c];
+    a.M[c] = P.emit(r.emit[c]).M;
+    a.tab[c] = rt->tabw + rt->tabw_off[c];
+  }
+  a.ebase = rt->ebase; a.A = d->A64; a.u0 = rt->u0;
+  a.T = T; a.N = N;
+  a.bp = reinterpret_cast<unsigned long long*>(d->S);
+  a.path_bstride = (long)T * a.nq; a.path_tstride = a.nq;
+  for (long b0 = 0; b0 < B; b0 += chunk) {
+    a.B = B - b0 < chunk ? B - b0 : chunk;
+    a.obs = d_obs ? d_obs + b0 * a.obs_bstride : nullptr;
+    a.path = d_path + b0 * a.path_bstride;
+    a.logp = d_logp ? d_logp + b0 : nullptr;
+    a.status = d_status ? d_status + b0 : nullptr;
+    if (int rc = nipamd::chain_viterbi_launch(a, (hipStream_t)stream)) return launch_fail(rc, "chain_viterbi_kernel");
+  }
+  return 0;
+}
+
+int nipamd_mlss(nipamd_model* mm, const int32_t* d_obs, int n_obs, const int* obs_vars, int B, int T,
+                int n_query, const int* query, int32_t* d_path, double* d_logp, uint32_t* d_status, void* stream) {
+  return mlss_impl(mm, d_obs, n_obs, obs_vars, B, T, n_query, query, d_path, d_logp, d_status, stream);
+}
+
+// host-buffer form of nipamd_mlss (copies in and out, synchronous)
+int nipamd_mlss_host(nipamd_model* mm, const int32_t* obs, int n_obs, const int* obs_vars, int B, int T,
+                     int n_query, const int* query, int32_t* path, double* logp, uint32_t* status) {
+  // the verdict on the request first: nothing is allocated for a refusal
+  {
+    nipamd::ViterbiArgs a{};
+    Route r;
+    if (int rc = mlss_check(mm, obs, n_obs, obs_vars, B, T, n_query, query, path, a, r)) return rc;
+  }
+  DevBufs db;
+  int32_t* d_obs = nullptr; int32_t* d_path = nullptr; double* d_lp = nullptr; uint32_t* d_st = nullptr;
+  const size_t nob = (size_t)B * T * (n_obs > 0 ? n_obs : 1);
+  const size_t npa = (size_t)B * T * (n_query > 0 ? n_query : 1);
+  if (int rc = db.alloc(&d_obs, nob)) return rc;
+  if (int rc = db.alloc(&d_path, npa)) return rc;
+  if (int rc = db.alloc(&d_lp, (size_t)B)) return rc;
+  if (int rc = db.alloc(&d_st, (size_t)B)) return rc;
+  if (n_obs > 0) HIP_OK(hipMemcpy(d_obs, obs, nob * sizeof(int32_t), hipMemcpyHostToDevice));
+  int rc = mlss_impl(mm, d_obs, n_obs, obs_vars, B, T, n_query, query, d_path, d_lp, d_st, nullptr);
+  if (rc == 0) {
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(path, d_path, npa * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (logp) HIP_OK(hipMemcpy(logp, d_lp, (size_t)B * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIP_OK(hipMemcpy(status, d_st, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return rc;
 }
 
 // The chain e_step kernels serve interface chains with evidence on their

@@ -1,0 +1,346 @@
+// viterbi.hip -- most likely state sequence of an interface chain (mlss, the
+// reference's declared and never implemented Viterbi / max-sum inference,
+// src/nip.h:431-438, src/nip.c:1620-1699), batched over sequences.
+//
+// Over the chain plan's tables (compile.cpp; the wide request tables of
+// engine.cpp ensure_req_tables) the marginal MAP of the interface sequence is
+//
+//   u0[y]      = sum_x pi[x] A[x][y]                     (host)
+//   e_t[y]     = ebase[y] prod_k tab_k[code_k,t][y]      (code: state, M = missing, M + 1 = out of range)
+//   delta_0[y] = u0[y] e_0[y]
+//   delta_t[y] = (max_x delta_{t-1}[x] A[x][y]) e_t[y],  psi_t[y] = the lowest x attaining the max
+//   x*_{T-1}   = the lowest y attaining max_y delta_{T-1}[y],  x*_{t-1} = psi_t[x*_t]
+//   logp       = ln max_y delta_{T-1}[y]
+//
+// in the probability domain, fp64, multiplies and compares only.  delta is
+// rescaled by an exact power of two every step -- the exponent of the row
+// maximum of delta_{t-1} is taken out of delta_t, one step late, so that the
+// reduction runs beside the products instead of ahead of them -- and the
+// exponents are summed into logp.  A power of two changes no comparison, so
+// ties (the lowest index wins) do not depend on the scaling or the lane layout.
+//
+// Layout: NP = 16, 32 or 64 padded states, one NP-lane group per sequence, lane
+// y = state y, 64 / NP sequences per wave, four independent waves per block.
+// Column y of A stays in registers.  delta_{t-1}[x] reaches every lane of its
+// group through a 64-bit DPP row_newbcast operand at NP = 16 (dpp_row.h's
+// v_fmac_f64_dpp onto a zero accumulator: fma(a, b, 0) is the rounded product)
+// and through the wave's own LDS row above that.  The evidence tables are
+// staged in LDS.  The raw observations of step t + 2 are loaded during step t
+// and only turned into table rows (and e_{t+2} read from LDS) at the top of
+// step t + 1, so each load has a whole step to land; the kernel is
+// instantiated per column count so that these loads sit in no branch.
+//
+// Back-pointers: log2(NP) bit planes per step, plane k = the wave's ballot of
+// bit k of psi_t -- one 64-bit word per plane covering all the wave's
+// sequences, 4 bits per state at NP = 16 (8 bytes per sequence and step; 20 and
+// 48 bytes at NP = 32 and 64).  A wave's words are contiguous in (t, plane)
+// order, collected in registers (lane l holds word l of the current run of
+// 64 / log2(NP) steps) and stored a run at a time.  The same wave backtracks:
+// it reloads its words a run ahead of their use -- the addresses do not depend
+// on the decoded states -- broadcasts each step's planes with v_readlane and
+// extracts bit (group base + x*_t) of each.  The path is collected 16 steps
+// per group and stored as int32, one column per queried variable (a joint
+// interface's digits).
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+
+#include "chain_kernels.h"
+#include "dpp_row.h"
+
+namespace nipamd {
+
+namespace {
+
+constexpr int kVitWaves = 4;
+
+__host__ __device__ constexpr int vit_log(int NP) { return NP == 16 ? 4 : NP == 32 ? 5 : 6; }
+// words of one wave: T steps of log2(NP) planes, padded to whole 128-byte lines
+__host__ __device__ inline long vit_wave_words(int NP, int T) { return ((long)T * vit_log(NP) + 15) & ~15L; }
+
+// acc[k] = fma(value of lane K0 + k of this row, c[K0 + k], acc[k]), k = 0..7.
+// One statement, so that the VALU -> DPP read hazard of v (2 wait states,
+// which hipcc does not pad inside asm) is covered once by the leading s_nop.
+template <int K0>
+__device__ __forceinline__ void fmac_bcast8(double (&p)[16], double v, const double (&c)[16]) {
+  asm("s_nop 1\n\t"
+      "v_fmac_f64_dpp %0, %8, %9 row_newbcast:%17 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %8, %10 row_newbcast:%18 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %2, %8, %11 row_newbcast:%19 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %3, %8, %12 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %4, %8, %13 row_newbcast:%21 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %5, %8, %14 row_newbcast:%22 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %6, %8, %15 row_newbcast:%23 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %7, %8, %16 row_newbcast:%24 row_mask:0xf bank_mask:0xf"
+      : "+v"(p[K0]), "+v"(p[K0 + 1]), "+v"(p[K0 + 2]), "+v"(p[K0 + 3]), "+v"(p[K0 + 4]), "+v"(p[K0 + 5]),
+        "+v"(p[K0 + 6]), "+v"(p[K0 + 7])
+      : "v"(v), "v"(c[K0]), "v"(c[K0 + 1]), "v"(c[K0 + 2]), "v"(c[K0 + 3]), "v"(c[K0 + 4]), "v"(c[K0 + 5]),
+        "v"(c[K0 + 6]), "v"(c[K0 + 7]), "n"(K0), "n"(K0 + 1), "n"(K0 + 2), "n"(K0 + 3), "n"(K0 + 4),
+        "n"(K0 + 5), "n"(K0 + 6), "n"(K0 + 7));
+}
+
+// the maximum over the 16 lanes of the row, in every lane
+__device__ __forceinline__ double row_max(double x) {
+  x = fmax(x, row_ror<8>(x));
+  x = fmax(x, row_ror<4>(x));
+  x = fmax(x, row_ror<2>(x));
+  x = fmax(x, row_ror<1>(x));
+  return x;
+}
+
+// max and lowest argmax of p[0..NP): four chains over ascending quarters,
+// merged in ascending order with a strict compare, so the lowest index wins
+template <int NP>
+__device__ __forceinline__ void argmax_low(const double (&p)[NP], double& best, int& arg) {
+  constexpr int Q = NP / 4;
+  double b[4];
+  int a[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    b[c] = p[c * Q];
+    a[c] = c * Q;
+#pragma unroll
+    for (int i = 1; i < Q; i++) {
+      const bool g = p[c * Q + i] > b[c];
+      a[c] = g ? c * Q + i : a[c];
+      b[c] = g ? p[c * Q + i] : b[c];
+    }
+  }
+  const bool g01 = b[1] > b[0], g23 = b[3] > b[2];
+  const double b01 = g01 ? b[1] : b[0], b23 = g23 ? b[3] : b[2];
+  const int a01 = g01 ? a[1] : a[0], a23 = g23 ? a[3] : a[2];
+  const bool g = b23 > b01;
+  best = g ? b23 : b01;
+  arg = g ? a23 : a01;
+}
+
+// One step for this lane's state y: m = the group's max of delta_{t-1} (d in
+// lane x = delta_{t-1}[x]), best / arg = max_x and lowest argmax_x of
+// delta_{t-1}[x] A[x][y].  xch: the wave's 64 doubles of LDS (NP > 16).
+template <int NP>
+__device__ __forceinline__ void vit_step(double d, const double (&Ac)[NP], double* xch, int lane, int gbase,
+                                         double& m, double& best, int& arg) {
+  double p[NP];
+  if constexpr (NP == 16) {
+#pragma unroll
+    for (int x = 0; x < 16; x++) p[x] = 0.0;
+    fmac_bcast8<0>(p, d, Ac);
+    fmac_bcast8<8>(p, d, Ac);
+    m = row_max(d);
+  } else {
+    // LDS operations of one wave complete in issue order: the wave's own row
+    // needs no barrier, only the compiler kept from reordering the accesses
+    xch[lane] = d;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    m = 0.0;
+#pragma unroll
+    for (int x = 0; x < NP; x++) {
+      const double dx = xch[gbase + x];
+      m = fmax(m, dx);
+      p[x] = dx * Ac[x];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  argmax_low<NP>(p, best, arg);
+}
+
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long w, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)w, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(w >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// NC = the observed columns (a.ncol): a constant, so that the observation loads
+// are unconditional and stay in flight over a whole step
+template <int NP, int NC>
+__global__ __launch_bounds__(kVitWaves * 64) void chain_viterbi_kernel(ViterbiArgs a) {
+  constexpr int LOG = vit_log(NP), SPF = 64 / LOG, RUN = SPF * LOG, G = 64 / NP;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* tabs = reinterpret_cast<double*>(smem);        // [rows][NP], ebase [NP], then [waves][64] (NP > 16)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = a.T;
+  constexpr int NCA = NC > 0 ? NC : 1;
+  int row0[NCA], rows = 0;
+#pragma unroll
+  for (int k = 0; k < NC; k++) {
+    row0[k] = rows;
+    const int n = (a.M[k] + 2) * NP;
+    for (int i = tid; i < n; i += kVitWaves * 64) tabs[rows * NP + i] = a.tab[k][(i / NP) * 64 + (i % NP)];
+    rows += a.M[k] + 2;
+  }
+  double* eb = tabs + rows * NP;
+  if (tid < NP) eb[tid] = a.ebase[tid];
+  double* xch = eb + NP + wave * 64;
+  __syncthreads();
+
+  const int grp = lane / NP, y = lane % NP, gbase = grp * NP;
+  const long gw = (long)blockIdx.x * kVitWaves + wave;   // the wave's sequences: gw G .. gw G + G - 1
+  if (gw * G >= a.B) return;
+  const long b = gw * G + grp;
+  const bool live = b < a.B;
+  const int* ob = a.obs + (live ? b : a.B - 1) * a.obs_bstride;
+
+  double Ac[NP];
+#pragma unroll
+  for (int x = 0; x < NP; x++) Ac[x] = a.A[x * 64 + y];
+
+  // Step t's raw observations (t clamped into the sequence): loads only, so
+  // that nothing waits for them here.  evid turns them into table rows and e_t
+  // a whole step later, where the wait for the loads lands.
+  auto fetch = [&](int t, int (&o)[NCA]) {
+    t = t < T ? t : T - 1;
+#pragma unroll
+    for (int k = 0; k < NC; k++) o[k] = ob[(long)t * a.obs_tstride + a.col[k]];
+  };
+  auto evid = [&](const int (&o)[NCA]) {
+    double e = eb[y];
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+      const int M = a.M[k];
+      e *= tabs[(row0[k] + (o[k] < 0 ? M : (o[k] < M ? o[k] : M + 1))) * NP + y];
+    }
+    return e;
+  };
+
+  int on[NCA] = {};
+  fetch(0, on);
+  double d = a.u0[y] * evid(on);                          // delta_0
+  fetch(1, on);
+  double en = evid(on);                                   // e_1
+  fetch(2, on);
+  long esum = 0;
+  unsigned long long* bpw = a.bp + gw * vit_wave_words(NP, T);
+  const long nwords = (long)T * LOG;
+  unsigned long long w = 0;                               // lane l: word l of the current run
+  int slot = LOG;                                         // step t's first word within the run
+  long wbase = 0;                                         // the run's first word
+  for (int t = 1; t < T; t++) {
+    const double e = en;
+    en = evid(on);                                        // e_{t+1}, from the observations fetched a step ago
+    fetch(t + 2, on);
+    double m, best;
+    int arg;
+    vit_step<NP>(d, Ac, xch, lane, gbase, m, best, arg);
+    int ex = 0;
+    (void)frexp(m, &ex);                                  // 0 for m == 0
+    d = ldexp(best * e, -ex);
+    esum += ex;
+#pragma unroll
+    for (int k = 0; k < LOG; k++) {
+      const unsigned long long bk = __ballot((arg >> k) & 1);
+      if (lane == slot + k) w = bk;
+    }
+    slot += LOG;
+    if (slot == RUN || t == T - 1) {
+      if (lane < RUN && wbase + lane < nwords) bpw[wbase + lane] = w;
+      wbase += RUN;
+      slot = 0;
+    }
+  }
+
+  // the final maximum, its lowest state, logp
+  double m;
+  if constexpr (NP == 16) {
+    m = row_max(d);
+  } else {
+    xch[lane] = d;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    m = 0.0;
+#pragma unroll
+    for (int x = 0; x < NP; x++) m = fmax(m, xch[gbase + x]);
+  }
+  const bool dead = !(m > 0.0);
+  unsigned long long hit = __ballot(d == m) >> gbase;
+  if (NP < 64) hit &= (1ull << (NP & 63)) - 1;
+  int x = hit ? __builtin_ctzll(hit) : 0;
+  if (live && y == 0) {
+    if (a.logp) a.logp[b] = dead ? -DBL_MAX : log(m) + (double)esum * 0.693147180559945309417232121458;
+    if (a.status) a.status[b] = dead ? 1u : 0u;
+  }
+
+  // backtrack: the wave's own words, read past the vector L1 (agent scope)
+  // once its stores have been made visible
+  __threadfence();
+  auto run_load = [&](int c) -> unsigned long long {
+    const long i = (long)c * RUN + lane;
+    if (c < 0 || lane >= RUN || i >= nwords) return 0ull;
+    return __hip_atomic_load(bpw + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  int c = (T - 1) / SPF;
+  unsigned long long wc = run_load(c), wn = run_load(c - 1);
+  int xs = 0;                                             // lane y < 16: x*_t of the step t = y (mod 16) in flight
+  int* prow = a.path + (live ? b : 0) * a.path_bstride;
+  for (int t = T - 1;; t--) {
+    if (y == (t & 15)) xs = x;
+    if ((t & 15) == 0 && live && y < 16 && t + y < T)
+      for (int j = 0; j < a.nq; j++)
+        prow[(long)(t + y) * a.path_tstride + j] = dead ? -1 : (xs / a.qstride[j]) % a.qcard[j];
+    if (t == 0) break;
+    if (t < c * SPF) {
+      c--;
+      wc = wn;
+      wn = run_load(c - 1);
+    }
+    const int s = (t - c * SPF) * LOG;
+    int xn = 0;
+#pragma unroll
+    for (int k = 0; k < LOG; k++) xn |= (int)((readlane64(wc, s + k) >> (gbase + x)) & 1) << k;
+    x = xn;
+  }
+}
+
+template <int NP, int NC>
+int vit_launch_nc(const ViterbiArgs& a, size_t lds, hipStream_t stream) {
+  static size_t lds_set[kMaxDevices] = {};
+  if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_viterbi_kernel<NP, NC>), lds, lds_set))
+    return rc;
+  const long waves = (a.B + 64 / NP - 1) / (64 / NP);
+  const dim3 grid((unsigned)((waves + kVitWaves - 1) / kVitWaves)), block(kVitWaves * 64);
+  hipLaunchKernelGGL((chain_viterbi_kernel<NP, NC>), grid, block, lds, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int NP>
+int vit_launch(const ViterbiArgs& a, size_t lds, hipStream_t stream) {
+  switch (a.ncol) {
+    case 0: return vit_launch_nc<NP, 0>(a, lds, stream);
+    case 1: return vit_launch_nc<NP, 1>(a, lds, stream);
+    case 2: return vit_launch_nc<NP, 2>(a, lds, stream);
+    case 3: return vit_launch_nc<NP, 3>(a, lds, stream);
+    default: return vit_launch_nc<NP, 4>(a, lds, stream);
+  }
+}
+
+int vit_np(int N) { return N <= 16 ? 16 : N <= 32 ? 32 : 64; }
+
+}  // namespace
+
+size_t chain_viterbi_scratch_bytes(int N, long B, int T) {
+  const int NP = vit_np(N), G = 64 / NP;
+  return (size_t)((B + G - 1) / G) * vit_wave_words(NP, T) * sizeof(unsigned long long);
+}
+
+size_t chain_viterbi_lds_bytes(const ViterbiArgs& a) {
+  const int NP = vit_np(a.N);
+  size_t rows = 1;                                         // ebase
+  for (int k = 0; k < a.ncol; k++) rows += (size_t)a.M[k] + 2;
+  return (rows * NP + (NP > 16 ? kVitWaves * 64 : 0)) * sizeof(double);
+}
+
+int chain_viterbi_launch(const ViterbiArgs& a, hipStream_t stream) {
+  if (a.N < 1 || a.N > 64 || a.ncol < 0 || a.ncol > 4 || a.nq < 1 || a.nq > kViterbiMaxQuery || a.B < 1 ||
+      a.B > 0x7fffffffL || a.T < 1)
+    return kLaunchRefused;
+  for (int k = 0; k < a.ncol; k++) if (a.M[k] < 1) return kLaunchRefused;
+  for (int j = 0; j < a.nq; j++) if (a.qstride[j] < 1 || a.qcard[j] < 1) return kLaunchRefused;
+  const size_t lds = (chain_viterbi_lds_bytes(a) + 15) & ~(size_t)15;
+  g_last_kernel = "chain_viterbi_kernel";
+  if (a.N <= 16) return vit_launch<16>(a, lds, stream);
+  if (a.N <= 32) return vit_launch<32>(a, lds, stream);
+  return vit_launch<64>(a, lds, stream);
+}
+
+}  // namespace nipamd
