@@ -307,7 +307,7 @@ struct EWideArgs {
   int ccol[4];           // their columns in obs, or -1 (never observed: always missing)
   int cM[4];
   int erow[4];           // first count-table row of each
-  int proper;            // rows of A and of every child sum to 1 (engine.cpp chain_proper): the
+  int proper;            // rows of A and of every child sum to 1 (engine_route.cpp chain_proper): the
                          // ll from the final forward mass, no per-step masses in the filters
 };
 int estep_wide_np(int N);
@@ -363,7 +363,7 @@ int estep_mw_launch(const EMwArgs& a, hipStream_t stream);
 // checkpoint + recompute e_step at 17..32 states (estep_ckw.hip, round 6):
 // one or two observed columns, the same wide slab row per 16 sequences;
 // count_rows = sum over the observed columns of M_k + 2.  Needs the host's
-// underflow bound for rescaling every 4th step (engine.cpp ckw_sparse_ok);
+// underflow bound for rescaling every 4th step (engine_route.cpp ckw_sparse_ok);
 // proper: ll from the final forward mass.  kLaunchRefused when it does not fit.
 size_t chain_estep_ckw_lds_bytes(int tab_rows, int count_rows);
 size_t chain_estep_ckw_scratch_bytes(long B, int T);

@@ -878,7 +878,7 @@ void build_joint_chain_plan(Model& m) {
   bool summed = false;
   for (int v = 0; v < nv; v++) summed |= role[v] == 3;
   // e_step on the HMM e_step kernel over the joint state, the slab projected
-  // onto every family (engine.cpp ensure_joint_map)
+  // onto every family (engine_estep.cpp ensure_joint_map)
   P.jhmm = !summed && cand.size() == 1 && K <= 16;
   P.joint = true;
   P.valid = true;

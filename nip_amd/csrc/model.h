@@ -102,7 +102,7 @@ struct ChainPlan {
   std::vector<int> jcur;            // joint: outgoing (their marginals: derive.hip kDeriveProject)
   // joint, <= 16 joint states, one observation candidate (emits[0]) and no
   // summed-out variable: the HMM e_step kernel runs on the joint state and the
-  // finalize projects the joint counts onto every family (engine.cpp)
+  // finalize projects the joint counts onto every family (engine_estep.cpp)
   bool jhmm = false;
 };
 constexpr long kGpuFoldMin = 1L << 22;
@@ -115,7 +115,7 @@ struct Model {
   std::vector<int> outgoing, previous_outgoing, independent, children;
 
   ChainPlan chain;
-  // device-side state (engine.cpp) and the general engine's caches (jtree_plan.cpp)
+  // device-side state (engine_dev.cpp) and the general engine's caches (jtree_plan.cpp)
   void* dev = nullptr;
   void* jt = nullptr;
 };
@@ -165,7 +165,7 @@ namespace nipamd {
 // parent j's table (keep = j: G_j [card][64][64]) summed on the current GPU
 int chain_fold_gpu(const Model& m, int keep, std::vector<double>& out, double* ms, double* bytes,
                    std::string& err);
-// engine.cpp: complete a deferred fold (ChainPlan::fold_gpu) before host use of A64
+// engine_dev.cpp: complete a deferred fold (ChainPlan::fold_gpu) before host use of A64
 int ensure_fold(nipamd_model* mm);
 // prefix.cpp: the first step k < T at which the reference's e_step rejects a
 // series that observed nothing at steps 0..k (-1: none)

@@ -299,7 +299,7 @@ int estep_prefix_first_bad(const Model& m, int T, int* steps) {
 }  // namespace nipamd
 
 namespace nipamd {
-// table entries one propagation touches (the engine's size cap, engine.cpp)
+// table entries one propagation touches (the engine's size cap, engine_estep.cpp)
 long estep_prefix_entries(const Model& m) {
   long n = 0;
   for (const Clique& c : m.cliques) n += table_size(m, c.vars);
