@@ -145,6 +145,14 @@ __device__ __forceinline__ v4d ldexp4(v4d v, int k) {
   return r;
 }
 
+// v with the entries zeroed whose entry of m is 0 (a select, never a product:
+// v may hold inf)
+__device__ __forceinline__ v4d zero_where_zero(v4d v, const v4d& m) {
+  v.x = m.x != 0.0 ? v.x : 0.0; v.y = m.y != 0.0 ? v.y : 0.0;
+  v.z = m.z != 0.0 ? v.z : 0.0; v.w = m.w != 0.0 ? v.w : 0.0;
+  return v;
+}
+
 // 1/c (v_rcp_f64 + two Newton steps); 0 when c == 0 so that an all-zero
 // array stays zero (nip_normalise_array, nippotential.c:354)
 __device__ __forceinline__ double recip(double c) {

@@ -338,6 +338,18 @@ __global__ __launch_bounds__(kCkThreads, 2) void chain_estep_ck_kernel(ChainArgs
   // recursion itself (no rescaling: its size follows alpha^'s).  Start:
   // beta~_{T-1} = 1 / z_T on the real states, z_T = sum_y alpha^_{T-1}
   // (0 for a dead or absent sequence: everything it adds is then 0).
+  // That size is bounded only where alpha^ is not 0.  A state the forward
+  // pass never reaches (zero prior, nothing leads into it) that fits the
+  // data better than the others would grow by the evidence ratio per step
+  // until it leaves the fp64 range, and the next mat-vec would multiply a
+  // structural 0 of A by inf.  So every full chunk first zeroes beta~_{4c+3}
+  // where the checkpoint alpha^_{4c+3} is 0.  Exact: alpha_t(y) = 0 means
+  // e_t(y) = 0 or alpha_{t-1}(x) A(x, y) = 0 for every x, so gamma_t(y),
+  // every xi_t(x, y) and y's term of beta_{t-1}(x) on every x with
+  // alpha_{t-1}(x) != 0 are 0 whatever beta_t(y) is -- and the entries
+  // beta_{t-1}(x) on the other x only ever meet zeros in the same way.
+  // Between two checkpoints such an entry grows by at most four steps'
+  // evidence ratios from the reachable entries' size.
   const double rz = recip(chain_sum(X));
   v4d Bt;                                       // beta~_t
   Bt.x = state_of(g, 0) < a.N ? rz : 0.0;
@@ -390,6 +402,7 @@ __global__ __launch_bounds__(kCkThreads, 2) void chain_estep_ck_kernel(ChainArgs
     const int kmax = FULL ? 3 : ((T - 1) & 3);
     v4d x = Cr;                                  // chunk c - 1's recomputation chain
     v4d nV[3];
+    if constexpr (FULL) Bt = zero_where_zero(Bt, C3);
 #pragma unroll
     for (int k = 3; k >= 0; k--) {
       if (FULL || k <= kmax) {                   // (the top chunk's steps past T - 1 skipped)

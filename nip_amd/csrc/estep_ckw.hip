@@ -375,7 +375,9 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
   };
 
   const int ctop = (T - 1) >> 2;
-  // beta~_{T-1} = 1 / z_T on the real states (estep_ck.hip)
+  // beta~_{T-1} = 1 / z_T on the real states; every full chunk zeroes it where
+  // its checkpoint is 0, which keeps the states the forward pass never
+  // reaches finite (estep_ck.hip)
   const double rz = recip(seq_sum(X));
   v4d Bt[NT];
 #pragma unroll
@@ -446,9 +448,11 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
   }
 
   // gamma_t normalised exactly (the reference's per-step posteriors) to
-  // post[b][t]: 16-byte pieces where the rows are 32 wide and aligned
-  const bool pvec = POST && a.post_tstride == NP && (a.post_off & 1) == 0 && (a.post_bstride & 1) == 0 &&
-                    (reinterpret_cast<uintptr_t>(a.post) & 15) == 0;
+  // post[b][t]: 16-byte pieces where the interface's 32 states are the whole
+  // aligned row (fewer states in a 32-wide row share it with other queries:
+  // the pieces would cover the padding states' slots, which are not ours)
+  const bool pvec = POST && a.N == NP && a.post_tstride == NP && (a.post_off & 1) == 0 &&
+                    (a.post_bstride & 1) == 0 && (reinterpret_cast<uintptr_t>(a.post) & 15) == 0;
   double* const prow = POST ? a.post + (size_t)(active ? b0 + j : 0) * a.post_bstride + a.post_off : nullptr;
   auto post_store = [&](int t, const v4d (&G)[NT]) {
     const double r = recip(seq_sum(G));
@@ -490,6 +494,9 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
     v4d x[NT] = {Cr[0], Cr[1]};                  // chunk c - 1's recomputation chain
     v4d nV[VL ? 1 : 3][NT];
     const int kmax = FULL ? 3 : ((T - 1) & 3);
+    if constexpr (FULL)                          // unreachable states: beta~ is 0 where the checkpoint is
+#pragma unroll
+      for (int q = 0; q < NT; q++) Bt[q] = zero_where_zero(Bt[q], C3[q]);
     // backward step k of chunk c
     auto bstep = [&](int k) {
       v4d curv[NT];

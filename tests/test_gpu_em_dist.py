@@ -179,6 +179,7 @@ def test_config4_full_shard_counts_vs_textbook():
     obs = torch.from_numpy(synth.observations(B, Tn, 16, seed=4)).cuda()
     ov = [m.variable("M1")]
     counts, ll, st = nip_amd.e_step(m, obs, ov, torch.zeros((m.param_size(),), dtype=torch.float64, device="cuda"))
+    assert nip_amd.last_kernel() == "chain_estep_ck_kernel", nip_amd.last_kernel()
     assert not st.any().item()
     A, pi, Es = chain_tables(m, m.variable("P0"), m.variable("P1"), [m.variable("M1")])
     tA, tpi, tE = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A, pi, Es[0]))

@@ -5,7 +5,8 @@ bound for rescaling every 4th step (engine.cpp estep16_sparse_ok).
 
 Against the CPU oracle (nip.c:1708-2007 restated, pinned to the reference by
 tests/test_oracle.py) on proper and non-proper models, every T mod 4, ragged
-batches, missing and out-of-range observations; at long T against the
+batches, missing and out-of-range observations, states the forward pass
+never reaches (T = 400: past the fp64 range of their backward entries); at long T against the
 textbook e_step in torch fp64; shard invariance of its partials (one slab row
 per 16 sequences, fixed-order trees).  Tolerances as tests/test_gpu_estep.py:
 counts rel 1e-11, ll rel 1e-12, BAD_LUCK flags exact.
@@ -49,6 +50,65 @@ def check_vs_oracle(m, obs, ov):
         c2, _, _ = gpu_estep(m, obs[ok], ov)
         rc2, _, _ = PortOracle(m.desc()).estep(obs[ok], ov, np.ones(m.param_size()))
         assert close(c2, rc2, CNT_RTOL), np.abs(c2 - rc2).max()
+
+
+def two_block_hmm(N, seed=5):
+    """An HMM whose states h..N-1 (h = N / 2) the forward pass never reaches:
+    zero prior and a block-diagonal transition, so nothing leads into them.
+    Symbol 0 is emitted with 0.1 on the reachable block and 0.9 on the other:
+    on a run of zeros the unreachable block's backward entries outgrow the
+    reachable block's by 9 per step.  Nodes child-first (hmm_spec's proper
+    order), so the compiled tables are the ones written here."""
+    h = N // 2
+    rng = np.random.default_rng(seed)
+    A = np.zeros((N, N))
+    A[:h, :h] = 0.05 + rng.random((h, h))
+    A[h:, h:] = 0.05 + rng.random((N - h, N - h))
+    A /= A.sum(axis=1, keepdims=True)
+    pi = np.zeros(N)
+    pi[:h] = 0.05 + rng.random(h)
+    pi /= pi.sum()
+    E = np.empty((N, 2))
+    E[:h] = (0.1, 0.9)
+    E[h:] = (0.9, 0.1)
+    nodes = [("M1", 2, None), ("P1", N, None), ("P0", N, "P1")]
+    pots = [("M1", ["P1"], E.ravel()), ("P1", ["P0"], A.ravel()), ("P0", [], pi)]
+    return nip_amd.Model.from_spec(nodes, pots)
+
+
+def two_block_obs(B, T):
+    """All symbol 0, a handful of missing steps (none first: the e_step's
+    verdict on a leading missing run is prefix.cpp's business)."""
+    obs = np.zeros((B, T, 1), np.int32)
+    for b in range(B):
+        obs[b, [5 + b, 77, T // 2 + 3 * b, T - 2 - b], 0] = -1
+    return obs
+
+
+@pytest.mark.parametrize("T", [400, 403])
+def test_ck_estep_unreachable_states_at_long_T(T):
+    """9^T leaves the fp64 range at T >= 323 (and 9^-T at T >= 340): a backward
+    message normalised against the forward one is unbounded on the states the
+    forward pass never reaches, and 0 x inf in the next mat-vec would turn
+    every count into NaN.  The kernel zeroes the backward entries of the
+    states whose checkpointed forward entry is 0 (estep_ck.hip): counts and ll
+    finite and the oracle's, no flag, and -- through the counts of the
+    unreachable block's emission rows -- no posterior mass there."""
+    N, h = 8, 4
+    m = two_block_hmm(N)
+    ov = [m.variable("M1")]
+    obs = two_block_obs(3, T)
+    rc, rl, rb = PortOracle(m.desc()).estep(obs, ov, np.ones(m.param_size()))
+    assert np.isfinite(rc).all() and np.isfinite(rl).all() and not rb.any()
+    cnt, ll, st = gpu_estep(m, obs, ov)
+    assert nip_amd.last_kernel() in (CK,), nip_amd.last_kernel()
+    assert np.isfinite(cnt).all() and np.isfinite(ll).all()
+    assert not st.any()
+    assert close(ll, rl, LL_RTOL), np.abs(ll - rl).max()
+    assert close(cnt, rc, CNT_RTOL), np.abs(cnt - rc).max()
+    # the counts the unreachable block adds are exactly 0: where the oracle
+    # keeps the pseudo-count 1.0, so does the GPU
+    assert np.array_equal(cnt[rc == 1.0], rc[rc == 1.0]) and (rc == 1.0).sum() >= 2 * (N - h)
 
 
 @pytest.mark.parametrize("proper", [False, True])

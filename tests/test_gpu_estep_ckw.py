@@ -6,7 +6,8 @@ rescaling bound holds (engine.cpp ckw_sparse_ok).
 Against the CPU oracle (nip.c:1708-2007 restated, pinned to the reference by
 tests/test_oracle.py) on proper and non-proper models, every T mod 4, ragged
 batches, missing and out-of-range observations, one and two columns, an
-unobserved child; at long T against the textbook e_step in torch fp64; shard
+unobserved child, states the forward pass never reaches; at long T against the
+textbook e_step in torch fp64; shard
 invariance of its partials; the same slab as chain_estep_mw_kernel (route tag
 (0, 0, 1)).  Tolerances as tests/test_gpu_estep_wide.py: counts rel 1e-11, ll
 rel 1e-12, BAD_LUCK flags exact.
@@ -110,6 +111,30 @@ def test_ckw_missing_and_invalid_vs_oracle():
     obs[8, 40, 1] = 99
     obs[36, 5:9] = -1
     check_vs_oracle(m, obs, ov)
+
+
+@pytest.mark.parametrize("T", [400, 403])
+def test_ckw_estep_unreachable_states_at_long_T(T):
+    """The two-block chain of test_gpu_estep_ck.py at 20 states: ten states the
+    forward pass never reaches, nine times likelier under every observation.
+    The backward message, normalised against the forward one, is zeroed where
+    the checkpoint is 0 (estep_ckw.hip), so nothing leaves the fp64 range:
+    counts and ll finite and the oracle's, no flag, no count on the
+    unreachable block."""
+    from test_gpu_estep_ck import two_block_hmm, two_block_obs
+    N, h = 20, 10
+    m = two_block_hmm(N)
+    ov = [m.variable("M1")]
+    obs = two_block_obs(3, T)
+    rc, rl, rb = PortOracle(m.desc()).estep(obs, ov, np.ones(m.param_size()))
+    assert np.isfinite(rc).all() and np.isfinite(rl).all() and not rb.any()
+    cnt, ll, st = gpu_estep(m, obs, ov)
+    assert nip_amd.last_kernel() in (CKW,), nip_amd.last_kernel()
+    assert np.isfinite(cnt).all() and np.isfinite(ll).all()
+    assert not st.any()
+    assert close(ll, rl, LL_RTOL), np.abs(ll - rl).max()
+    assert close(cnt, rc, CNT_RTOL), np.abs(cnt - rc).max()
+    assert np.array_equal(cnt[rc == 1.0], rc[rc == 1.0]) and (rc == 1.0).sum() >= 2 * (N - h)
 
 
 def test_ckw_is_the_config3_default():

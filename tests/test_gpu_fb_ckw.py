@@ -10,8 +10,8 @@ the reference's own fixture (fb_demo1.npz at card 4 is the 16-state kernel's;
 here 17..32 states): every T mod 4, ragged batches, proper and non-proper
 models, missing and out-of-range observations, one and two columns, queries
 on the interface and on derived variables (a child, the hidden parent, the
-previous slice); the same posteriors as chain_mfma_wide_kernel (diagnostics
-build switch).  Tolerances as tests/test_gpu_wide.py: posteriors 1e-12
+previous slice), states the forward pass never reaches at T = 400; the same
+posteriors as chain_mfma_wide_kernel (diagnostics build switch).  Tolerances as tests/test_gpu_wide.py: posteriors 1e-12
 absolute, ll 1e-11 relative at 32 states.
 """
 import os
@@ -106,6 +106,32 @@ def test_fb_ckw_missing_and_invalid_vs_oracle():
     obs[5, 0, 1] = 77
     obs[8, ::2, 1] = -1
     check_vs_oracle(m, obs, ov, [m.variable("C1")])
+
+
+@pytest.mark.parametrize("T", [400, 403])
+def test_fb_ckw_unreachable_states_at_long_T(T):
+    """The two-block chain of test_gpu_estep_ck.py at 20 states: ten states the
+    forward pass never reaches, nine times likelier under every observation
+    (9^T is past the fp64 range at T >= 323).  The backward message is zeroed
+    where the checkpoint is 0 (estep_ckw.hip): posteriors and ll finite and
+    the oracle's, no flag, and exactly no mass on the unreachable block."""
+    from test_gpu_estep_ck import two_block_hmm, two_block_obs
+    N, h = 20, 10
+    m = two_block_hmm(N)
+    ov, q = [m.variable("M1")], [m.variable("P1")]
+    obs = two_block_obs(3, T)
+    post, ll, st = gpu_fb(m, obs, ov, q)
+    assert nip_amd.last_kernel() in (FBCK,), nip_amd.last_kernel()
+    assert np.isfinite(post).all() and np.isfinite(ll).all()
+    assert not st.any()
+    orc = PortOracle(m.desc())
+    for b in range(obs.shape[0]):
+        rp, rl = orc.fb(obs[b], ov, q)
+        assert np.isfinite(rp).all() and np.isfinite(rl)
+        err = np.abs(post[b] - rp).max()
+        assert err <= 1e-12, "sequence %d: posterior error %g" % (b, err)
+        assert abs(ll[b] - rl) <= 1e-11 * max(1.0, abs(rl)), (b, ll[b], rl)
+    assert not post[:, :, h:].any()
 
 
 def test_fb_ckw_is_the_config3_default_and_rows_sum_to_one():

@@ -80,6 +80,42 @@ def test_em_learn_ragged_series_vs_oracle():
         params = counts
 
 
+def test_estep_ragged_series_with_leading_missing_runs_vs_oracle():
+    """The ragged series of the test above, two of them starting with a run of
+    missing steps (the reference's BAD_LUCK verdict on such a prefix,
+    prefix.cpp): one e_step per series on chain_estep_ck_kernel against the
+    oracle's, on the tables of one m_step that both sides read from the model
+    -- before a second m_step could let an ulp of the learned tables flip a
+    flag.  Flags exact, ll rel 1e-12, counts rel 1e-11 (test_gpu_estep_ck.py)."""
+    import torch
+    nodes, pots = synth.hmm_spec(6, 5, seed=21)
+    m = nip_amd.Model.from_spec(nodes, pots)
+    ov = [m.variable("M1")]
+    rng = np.random.default_rng(3)
+    series = [rng.integers(-1, 5, size=(T, 1)).astype(np.int32) for T in (5, 1, 17, 5, 33, 2, 9, 17)]
+    for s in series:
+        s[0, 0] = abs(int(s[0, 0]))
+    series[2][:3, 0] = -1                          # T = 17: three leading missing steps (accepted)
+    series[4][:31, 0] = -1                         # T = 33: 31, which the reference rejects
+    m.m_step(rng.random(m.param_size()))
+    orc = PortOracle(m.desc())
+    flags = []
+    for i, s in enumerate(series):
+        cnt, ll, st = nip_amd.e_step(m, torch.from_numpy(s[None]).cuda(), ov)
+        torch.cuda.synchronize()
+        assert nip_amd.last_kernel() == "chain_estep_ck_kernel", nip_amd.last_kernel()
+        cnt, ll, st = cnt.cpu().numpy(), ll.cpu().numpy(), st.cpu().numpy()
+        rc, rl, rb = orc.estep(s[None], ov, np.ones(m.param_size()))
+        print("series %d (T = %d): status %d, oracle's flag %d" % (i, len(s), st[0], rb[0]))
+        assert (st[0] != 0) == (rb[0] != 0), (i, st.tolist(), rb.tolist())
+        flags.append(int(rb[0]))
+        if rb[0]:
+            continue
+        assert abs(ll[0] - rl[0]) <= 1e-12 * max(1.0, abs(rl[0])), (i, ll[0], rl[0])
+        assert np.all(np.abs(cnt - rc) <= 1e-11 * np.maximum(1.0, np.abs(rc))), (i, np.abs(cnt - rc).max())
+    assert flags == [0, 0, 0, 0, 1, 0, 0, 0]       # both verdicts on a leading run were met
+
+
 def libc_rand_init(seed, P, runs=1):
     libc = ctypes.CDLL("libc.so.6")
     libc.srand(ctypes.c_uint(seed))

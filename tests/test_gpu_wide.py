@@ -134,7 +134,8 @@ def test_config3_scale_properties():
 
 def test_config3_full_size_properties_and_parity():
     """Config 3 at its bench size: demo1 @ 32 states, 65,536 sequences x
-    T=256 (chain_mfma_wide_kernel<2>: every launch-grid and LDS path at full B).  Normalised posteriors, finite
+    T=256 (smoothing on chain_fb_ckw_kernel, the benchmark's kernel; filtering
+    on chain_mfma_wide_kernel<2>: every launch-grid and LDS path at full B).  Normalised posteriors, finite
     ll <= 0, filter ll == smoothing ll and the last filtered step == the last
     smoothed step; 1,024 sequences spread over the batch (first and last
     block included) against the textbook smoother over the model's own
@@ -149,7 +150,9 @@ def test_config3_full_size_properties_and_parity():
     obs_np[1000, 100:140, 0] = -1
     obs = torch.from_numpy(obs_np).cuda()
     post, ll, st = nip_amd.forward_backward_inference(m, obs, ov, q)
+    assert nip_amd.last_kernel() == "chain_fb_ckw_kernel", nip_amd.last_kernel()
     fpost, fll, fst = nip_amd.forward_inference(m, obs, ov, q)
+    assert nip_amd.last_kernel() == "chain_mfma_wide_kernel<2>", nip_amd.last_kernel()
     torch.cuda.synchronize()
     assert not st.any().item() and not fst.any().item()
     s = post.sum(dim=2)
