@@ -521,6 +521,75 @@ int nipamd_mlss_host(nipamd_model* m, const int32_t* obs, int n_obs,
                      const int* query, int32_t* path, double* logp,
                      uint32_t* status);
 
+/*
+ * Online inference: resumable filtering and fixed-lag smoothing.  The
+ * reference's authors list online forward_inference and online fixed-lag
+ * smoothing as what the library still lacks (TODO.org); every batched entry
+ * point above needs the whole sequence up front.
+ *
+ * A stream is opened for (model, observed columns, query, B sequences, lag L)
+ * and fed steps; the B sequences advance in lockstep.  With n the steps
+ * consumed so far and n_end the steps consumed when the stream is flushed,
+ *
+ *   row t = the marginal of the queried variables at step t given
+ *           y_0 .. y_{min(t + L, n_end - 1)}
+ *
+ * -- nipamd_filter's row at L = 0, nipamd_fb's at L >= n_end - 1.  Row t is
+ * emitted by the push that consumes step t + L, or by the flush: a push of T
+ * steps emits E = max(0, pending + T - L) rows per sequence, pending =
+ * min(n, L), densely as [B][E][width], width = the summed cardinalities of
+ * the query (nipamd_fb's row layout); a flush emits the `pending` rows left.
+ * ll is the running sum of log m2_t - log m1_t over the consumed steps
+ * (nipamd_filter's ll of those steps); status is sticky.  A sequence whose
+ * evidence leaves no mass at step d gets NIPAMD_STATUS_ZERO_MASS and ll =
+ * -DBL_MAX from then on, and every row t with min(t + L, n_end - 1) >= d is
+ * all zeros; rows emitted earlier and the other sequences are unaffected.
+ * Rows, ll and status depend only on the sequence of steps, bit for bit: not
+ * on how the steps were split into pushes or the batch into streams.
+ *
+ * Scope (decided by nipamd_stream_open on the host, before the device is
+ * touched; NIPAMD_ERROR_UNSUPPORTED with the condition in nipamd_last_error):
+ * a model with an interface-chain plan, not set to NIPAMD_ENGINE_JTREE;
+ * evidence the chain plan routes (at most four columns, each the interface
+ * variable or a leaf child); a query that is a non-empty list of distinct
+ * current-slice interface variables (the interface variable, or members of a
+ * joint interface: any subset, any order); tables and lag that fit a CU's
+ * LDS.  NULL pointers: NIP_ERROR_NULLPOINTER.  B < 1, a lag outside
+ * 0..NIPAMD_STREAM_MAX_LAG, a variable index out of range:
+ * NIP_ERROR_INVALID_ARGUMENT.
+ *
+ * A push uses the model's tables as they are at that push.  Calls are
+ * asynchronous on `stream`; the calls of one nipamd_stream are ordered by the
+ * caller (one HIP stream, or events).  n and pending are host counters,
+ * updated at call time.  d_ll / d_status: NULL, or [B] receiving the running
+ * totals.  d_post may be NULL only when the call emits nothing
+ * (NIP_ERROR_NULLPOINTER otherwise).  T < 1, and a push after a flush (until
+ * nipamd_stream_reset), are NIP_ERROR_INVALID_ARGUMENT.  Free the streams of
+ * a model before the model.
+ */
+typedef struct nipamd_stream nipamd_stream;
+#define NIPAMD_STREAM_MAX_LAG 64
+#define NIPAMD_STREAM_CHUNK   64   /* steps per kernel launch; a longer push runs as consecutive launches */
+
+int nipamd_stream_open(nipamd_model* m, int n_obs, const int* obs_vars, int n_query,
+                       const int* query, int B, int lag, nipamd_stream** out);
+int nipamd_stream_push(nipamd_stream* s, const int32_t* d_obs /* [B][T][n_obs] */, int T,
+                       double* d_post /* [B][E][width] */, double* d_ll, uint32_t* d_status,
+                       void* stream);
+int nipamd_stream_flush(nipamd_stream* s, double* d_post /* [B][pending][width] */,
+                        double* d_ll, uint32_t* d_status, void* stream);
+/* back to the prior, n = 0 */
+int nipamd_stream_reset(nipamd_stream* s, void* stream);
+/* min(n, lag), 0 after a flush; -1 for NULL */
+int nipamd_stream_pending(const nipamd_stream* s);
+/* n; -1 for NULL */
+long nipamd_stream_steps(const nipamd_stream* s);
+void nipamd_stream_free(nipamd_stream* s);
+/* Host-buffer forms (copy in and out and synchronise). */
+int nipamd_stream_push_host(nipamd_stream* s, const int32_t* obs, int T, double* post,
+                            double* ll, uint32_t* status);
+int nipamd_stream_flush_host(nipamd_stream* s, double* post, double* ll, uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ from . import build as _build
 
 __all__ = ["NipError", "Model", "parse_model", "lib", "forward_backward_inference",
            "forward_backward_inference_host", "forward_inference", "forward_inference_host",
-           "most_likely_states", "most_likely_states_host",
+           "most_likely_states", "most_likely_states_host", "Stream",
            "e_step", "estep_partial", "estep_finalize", "em_learn", "read_timeseries",
            "write_uncertainseries", "write_model", "em_learn_series", "LIB_PATH"]
 
@@ -42,6 +42,8 @@ STATUS_BAD_LUCK = 2
 ENGINE_AUTO = 0          # interface-chain kernels where they apply, else the general engine
 ENGINE_CHAIN = 1         # interface-chain kernels only
 ENGINE_JTREE = 2         # the general join-tree engine for every request
+STREAM_MAX_LAG = 64      # NIPAMD_STREAM_MAX_LAG
+STREAM_CHUNK = 64        # NIPAMD_STREAM_CHUNK: steps per kernel launch of a push
 
 # every entry point declared in include/nip_amd.h
 EXPORTS = [
@@ -64,6 +66,9 @@ EXPORTS = [
     "nipamd_model_num_cliques", "nipamd_model_num_sepsets", "nipamd_model_clique",
     "nipamd_model_sepset", "nipamd_model_interface_cliques", "nipamd_model_set_tables", "nipamd_model_fold",
     "nipamd_mlss", "nipamd_mlss_host",
+    "nipamd_stream_open", "nipamd_stream_push", "nipamd_stream_flush", "nipamd_stream_reset",
+    "nipamd_stream_pending", "nipamd_stream_steps", "nipamd_stream_free",
+    "nipamd_stream_push_host", "nipamd_stream_flush_host",
 ]
 
 
@@ -104,6 +109,17 @@ def lib():
         L.nipamd_filter_host.argtypes = L.nipamd_fb_host.argtypes
         L.nipamd_mlss.argtypes = L.nipamd_fb.argtypes
         L.nipamd_mlss_host.argtypes = L.nipamd_fb_host.argtypes
+        L.nipamd_stream_open.argtypes = [vp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.POINTER(vp)]
+        L.nipamd_stream_push.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+        L.nipamd_stream_flush.argtypes = [vp, vp, vp, vp, vp]
+        L.nipamd_stream_reset.argtypes = [vp, vp]
+        L.nipamd_stream_pending.argtypes = [vp]
+        L.nipamd_stream_steps.argtypes = [vp]
+        L.nipamd_stream_steps.restype = C.c_long
+        L.nipamd_stream_free.argtypes = [vp]
+        L.nipamd_stream_free.restype = None
+        L.nipamd_stream_push_host.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+        L.nipamd_stream_flush_host.argtypes = [vp, vp, vp, vp]
         L.nipamd_estep.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_int, vp, vp, vp, vp]
         L.nipamd_estep_partial_size.argtypes = [vp]
         if hasattr(L, "nipamd_estep_partial_size_req"):      # (absent from A/B builds of older revisions)
@@ -452,6 +468,131 @@ def most_likely_states_host(model: Model, obs, obs_vars, query):
                                   B, T, len(query), _ints(query), path.ctypes.data_as(C.c_void_p),
                                   logp.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
     return path, logp, status
+
+
+class Stream:
+    """Online inference over B sequences that advance in lockstep: resumable
+    filtering (lag = 0) and fixed-lag smoothing (nipamd_stream_*).
+
+    Row t is the marginal of the query variables at step t given the evidence
+    of steps 0 .. t + lag (at a flush: up to the last step consumed).  A push
+    of T steps returns the E = max(0, pending + T - lag) rows whose lag it
+    consumed, [B, E, sum card(query)]; flush() returns the `pending` rows
+    left.  ``ll`` and ``status`` hold the running totals after the last call
+    (CUDA tensors [B], written asynchronously on the call's stream).  Rows, ll
+    and status do not depend on how the steps are split into pushes.
+
+    query: the model's interface variable, or members of a joint interface (any
+    subset, any order).  The stream keeps its Model alive; close() (or the
+    context manager) frees the device state.
+    """
+
+    def __init__(self, model: Model, obs_vars, query, B: int, lag: int = 0):
+        self._h = None
+        self.model = model
+        self.obs_vars = [int(v) for v in obs_vars]
+        self.query = [int(v) for v in query]
+        self.B, self.lag = int(B), int(lag)
+        h = C.c_void_p()
+        _check(lib().nipamd_stream_open(model._h, len(self.obs_vars), _ints(self.obs_vars), len(self.query),
+                                        _ints(self.query), self.B, self.lag, C.byref(h)))
+        self._h = h
+        self.width = sum(model.card(v) for v in self.query)
+        import torch
+        self.ll = torch.zeros((self.B,), dtype=torch.float64, device="cuda")
+        self.status = torch.zeros((self.B,), dtype=torch.int32, device="cuda")
+
+    def _handle(self):
+        if not self._h:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "the stream is closed")
+        return self._h
+
+    @property
+    def steps(self) -> int:
+        """Steps consumed so far."""
+        return lib().nipamd_stream_steps(self._handle())
+
+    @property
+    def pending(self) -> int:
+        """Rows still owed: min(steps, lag), 0 after a flush."""
+        return lib().nipamd_stream_pending(self._handle())
+
+    def push(self, obs, post=None, stream=None):
+        """obs: torch int32 CUDA tensor [B, T, n_obs] (state index, <0 missing), T >= 1."""
+        import torch
+        h = self._handle()
+        if obs.dim() == 2:
+            obs = obs.unsqueeze(-1)
+        if (obs.dtype != torch.int32 or not obs.is_cuda or not obs.is_contiguous() or obs.dim() != 3
+                or obs.shape[0] != self.B or obs.shape[2] != len(self.obs_vars)):
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT,
+                           "obs must be a contiguous int32 CUDA tensor of shape (%d, T, %d)"
+                           % (self.B, len(self.obs_vars)))
+        T = int(obs.shape[1])
+        E = max(0, self.pending + T - self.lag)
+        post = _out_buf(post, (self.B, E, self.width), torch.float64, obs.device, "post")
+        _check(lib().nipamd_stream_push(h, C.c_void_p(obs.data_ptr()), T,
+                                        C.c_void_p(post.data_ptr() if E else 0),
+                                        C.c_void_p(self.ll.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                        _stream_ptr(stream)))
+        return post
+
+    def flush(self, post=None, stream=None):
+        """The rows left, each given every step consumed; then only reset() or close()."""
+        import torch
+        h = self._handle()
+        E = self.pending
+        post = _out_buf(post, (self.B, E, self.width), torch.float64, self.ll.device, "post")
+        _check(lib().nipamd_stream_flush(h, C.c_void_p(post.data_ptr() if E else 0),
+                                         C.c_void_p(self.ll.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                         _stream_ptr(stream)))
+        return post
+
+    def push_host(self, obs):
+        """push from a host numpy array [B, T, n_obs]: (post, ll, status) as numpy (synchronous)."""
+        h = self._handle()
+        obs = np.ascontiguousarray(np.asarray(obs, np.int32))
+        if obs.ndim == 2:
+            obs = obs[:, :, None]
+        if obs.ndim != 3 or obs.shape[0] != self.B or obs.shape[2] != len(self.obs_vars):
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs must have shape (%d, T, %d)" % (self.B, len(self.obs_vars)))
+        T = int(obs.shape[1])
+        post = np.zeros((self.B, max(0, self.pending + T - self.lag), self.width))
+        ll, status = np.zeros(self.B), np.zeros(self.B, np.uint32)
+        _check(lib().nipamd_stream_push_host(h, obs.ctypes.data_as(C.c_void_p), T, post.ctypes.data_as(C.c_void_p),
+                                             ll.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+        return post, ll, status
+
+    def flush_host(self):
+        h = self._handle()
+        post = np.zeros((self.B, self.pending, self.width))
+        ll, status = np.zeros(self.B), np.zeros(self.B, np.uint32)
+        _check(lib().nipamd_stream_flush_host(h, post.ctypes.data_as(C.c_void_p), ll.ctypes.data_as(C.c_void_p),
+                                              status.ctypes.data_as(C.c_void_p)))
+        return post, ll, status
+
+    def reset(self, stream=None):
+        """Back to the prior: no step consumed, ll = 0, status = 0."""
+        _check(lib().nipamd_stream_reset(self._handle(), _stream_ptr(stream)))
+        self.ll.zero_()
+        self.status.zero_()
+
+    def close(self):
+        if self._h:
+            lib().nipamd_stream_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def generate_order(model: Model):

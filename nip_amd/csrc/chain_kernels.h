@@ -242,6 +242,63 @@ size_t chain_viterbi_scratch_bytes(int N, long B, int T);
 size_t chain_viterbi_lds_bytes(const ViterbiArgs& a);
 int chain_viterbi_launch(const ViterbiArgs& a, hipStream_t stream);
 
+// online inference (stream.hip, chain_stream_kernel): one launch advances every
+// sequence of a stream by T_new <= kStreamChunk steps from the state the last
+// launch left on the device, and emits the rows whose lag has been consumed.
+// Per sequence the state holds the base message alpha^_{s-1} (s = the oldest
+// pending step), the head message alpha^_{n-1}, the running ll (as the product
+// of the m2 over the product of the m1: two mantissas and an exponent sum), the
+// sticky status, the first step without mass and a ring of the pending steps'
+// raw codes (step t in slot t % lag).  Tables as ViterbiArgs (the wide request
+// tables); the query columns are digits of the interface state.
+constexpr int kStreamChunk = 64;
+constexpr int kStreamMaxLag = 64;
+constexpr long kStreamAlive = 0x7fffffffffffffffL;   // "first step without mass" of a live sequence
+struct StreamArgs {
+  const int* obs;        // int32 observations of the new steps [B][T_new ..][n_obs]
+  long obs_bstride;      // elements between sequences
+  int obs_tstride;       // elements between time steps
+  int ncol;              // observed columns
+  int col[4];            // their columns in obs
+  int M[4];              // their cardinalities
+  const double* tab[4];  // [(M+2)][64] per column: E, then the row sums, then 0
+  const double* ebase;   // [64] product of the unobserved children's row sums
+  const double* A;       // [64][64]
+  const double* sall;    // [64] product of every child's row sums
+  long B;
+  int N;
+  int lag;               // L
+  int pending;           // min(n, L): steps n - pending .. n - 1 wait in the ring
+  int T_new;             // new steps of this launch (0: a flush)
+  int final;             // a flush: the rows left end at step n - 1
+  int E;                 // rows emitted: max(0, pending + T_new - L), or pending for a flush
+  long n;                // steps consumed before this launch
+  // the state (one allocation per stream, engine_stream.cpp)
+  double* base;          // [B][NP]
+  double* head;          // [B][NP]
+  double* snum;          // [B] ll = log snum - log sden + sexp ln 2
+  double* sden;          // [B]
+  long* sexp;            // [B]
+  unsigned* sstatus;     // [B]
+  long* sdead;           // [B]
+  int* ring;             // [B][lag][ncol]
+  double* post;          // rows [B][..][width], the launch's first row at post
+  long post_bstride;     // elements between sequences
+  int post_tstride;      // elements between rows (width)
+  int nq;                // queried variables; nq == 0: the interface state itself (width N)
+  int qstride[kViterbiMaxQuery], qcard[kViterbiMaxQuery];
+  double* ll;            // [B] or nullptr: the running total after this launch
+  unsigned* status;      // [B] or nullptr
+};
+int chain_stream_np(int N);
+// LDS of a launch with these tables, columns and lag (any T_new, pending)
+size_t chain_stream_lds_bytes(const StreamArgs& a);
+// the dynamic-LDS limit of the kernel that serves a (ensure_dyn_lds): 0, or a refusal / failure
+int chain_stream_prepare(const StreamArgs& a);
+int chain_stream_launch(const StreamArgs& a, hipStream_t stream);
+// base = head = pi, ll = 0, status = 0, no dead step
+int chain_stream_init_launch(const StreamArgs& a, const double* pi64, hipStream_t stream);
+
 // generate_data (generate.hip): one sampling step per variable, in sampling
 // order.  In the first slice the conditional row of step i starts at
 // tab[off0 + idx], idx = sum_c value(ctx[c]) * stride[c] (in elements) with

@@ -1,0 +1,242 @@
+// engine_stream.cpp -- online inference: the nipamd_stream_* entry points over
+// chain_stream_kernel (stream.hip).  A stream owns the per-sequence state on
+// the device (forward messages, running totals, the ring of pending codes) and
+// the host counters n and pending; the model's tables are looked up per call,
+// as every entry point does (engine_internal.h).
+#include <algorithm>
+
+#include "engine_internal.h"
+
+using namespace nipamd::eng;
+
+// The opaque handle of the C-ABI (include/nip_amd.h).
+struct nipamd_stream {
+  nipamd_model* mm = nullptr;
+  std::vector<int> obs_vars;
+  int B = 0, lag = 0, width = 0;
+  Route r;
+  nipamd::StreamArgs a{};       // the launch arguments that never change: shape, query digits, state
+  void* state = nullptr;        // one device allocation behind a.base .. a.ring
+  long n = 0;                   // steps consumed
+  int pending = 0;              // min(n, lag); 0 after a flush
+  bool flushed = false;
+};
+
+namespace {
+
+static_assert(NIPAMD_STREAM_CHUNK == nipamd::kStreamChunk && NIPAMD_STREAM_MAX_LAG == nipamd::kStreamMaxLag,
+              "include/nip_amd.h and chain_kernels.h disagree");
+
+// The verdict on a stream -- the arguments, then the scope -- decided on the
+// host before anything touches the device (as mlss_check).  Fills the route,
+// the query digits and the shape of s.
+int stream_check(nipamd_model* mm, int n_obs, const int* obs_vars, int n_query, const int* query, int B, int lag,
+                 nipamd_stream** out, nipamd_stream& s) {
+  if (!mm || !out || (n_obs > 0 && !obs_vars) || (n_query > 0 && !query))
+    return fail(NIP_ERROR_NULLPOINTER, "stream: NULL model, variables or result");
+  if (B < 1 || lag < 0 || lag > NIPAMD_STREAM_MAX_LAG || n_obs < 0 || n_query < 0)
+    return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad arguments (B >= 1, 0 <= lag <= " +
+                                                std::to_string(NIPAMD_STREAM_MAX_LAG) + ")");
+  const int nv = (int)mm->m.vars.size();
+  for (int i = 0; i < n_obs; i++)
+    if (obs_vars[i] < 0 || obs_vars[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad observed variable");
+  for (int i = 0; i < n_query; i++)
+    if (query[i] < 0 || query[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad query variable");
+  const auto& P = mm->m.chain;
+  if (mm->engine == NIPAMD_ENGINE_JTREE)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: the engine is set to NIPAMD_ENGINE_JTREE; online inference runs "
+                                          "on the interface-chain plan only");
+  if (!P.valid)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: model slice is not an interface chain (no chain plan; the operator "
+                                          "chain and the general engine have no online form; see DESIGN.md)");
+  std::string why;
+  if (!route_request(mm, n_obs, obs_vars, 0, nullptr, s.r, why)) return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: " + why);
+  // the query: distinct current-slice interface variables, at least one
+  nipamd::StreamArgs& a = s.a;
+  bool is_if = n_query >= 1;
+  if (!P.joint) {
+    is_if = n_query == 1 && query[0] == P.v_cur;
+    a.nq = 0;
+    s.width = P.N;
+  } else {
+    is_if &= n_query <= nipamd::kViterbiMaxQuery;
+    s.width = 0;
+    for (int j = 0; is_if && j < n_query; j++) {
+      int k = -1, stride = 1;
+      for (size_t i = 0; i < P.jcur.size(); i++) if (P.jcur[i] == query[j]) k = (int)i;
+      for (int i = 0; i < j; i++) is_if &= query[i] != query[j];
+      if (k < 0) { is_if = false; break; }
+      for (int i = 0; i < k; i++) stride *= mm->m.vars[P.jcur[i]].card;
+      a.qstride[j] = stride; a.qcard[j] = mm->m.vars[query[j]].card;
+      s.width += a.qcard[j];
+    }
+    a.nq = n_query;
+  }
+  if (!is_if)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: the query is not a non-empty list of distinct current-slice "
+                                          "interface variables (at most " +
+                                              std::to_string(nipamd::kViterbiMaxQuery) + ")");
+  a.B = B; a.N = P.N; a.lag = lag;
+  a.ncol = s.r.ncol;
+  for (int i = 0; i < s.r.ncol; i++) { a.col[i] = s.r.col[i]; a.M[i] = P.emit(s.r.emit[i]).M; }
+  a.post_tstride = s.width;
+  const int rc = nipamd::chain_stream_prepare(a);
+  if (rc == nipamd::kLaunchRefused)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: the evidence tables, the transition and the window of lag " +
+                                              std::to_string(lag) + " need " +
+                                              std::to_string(nipamd::chain_stream_lds_bytes(a)) +
+                                              " bytes of LDS, more than a CU holds");
+  if (rc) return launch_fail(rc, "chain_stream_kernel");
+  s.mm = mm; s.B = B; s.lag = lag;
+  s.obs_vars.assign(obs_vars, obs_vars + n_obs);
+  return 0;
+}
+
+// the tables of this call into a (a push uses the model's tables as they are now)
+int stream_tables(nipamd_stream* s, nipamd::StreamArgs& a) {
+  nipamd_model* mm = s->mm;
+  if (int rc = ensure_tables(mm)) return rc;           // (the GPU fold of a fold_gpu plan included)
+  ReqTables* rt = nullptr;
+  if (int rc = ensure_req_tables(mm, s->r, &rt)) return rc;
+  const DevState* d = dev_of(mm);
+  set_cols(a, mm->m.chain, s->r, *rt);
+  a.A = d->A64; a.sall = d->sall64;
+  return 0;
+}
+
+int stream_reset(nipamd_stream* s, void* stream) {
+  nipamd::StreamArgs a = s->a;
+  if (int rc = stream_tables(s, a)) return rc;
+  if (int rc = nipamd::chain_stream_init_launch(a, dev_of(s->mm)->pi64, (hipStream_t)stream))
+    return launch_fail(rc, "chain_stream_init_kernel");
+  s->n = 0; s->pending = 0; s->flushed = false;
+  return 0;
+}
+
+int rows_of_push(const nipamd_stream* s, int T) { return std::max(0L, (long)s->pending + T - s->lag); }
+
+// the argument verdict of a push / flush (host or device buffers: only tested for NULL)
+int push_check(const nipamd_stream* s, const void* obs, int T, const void* post) {
+  if (!s) return fail(NIP_ERROR_NULLPOINTER, "stream: NULL stream");
+  if (T < 1) return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: a push takes at least one step");
+  if (s->flushed) return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: push after flush (nipamd_stream_reset starts over)");
+  if (!s->obs_vars.empty() && !obs) return fail(NIP_ERROR_NULLPOINTER, "stream: NULL observations");
+  if (rows_of_push(s, T) > 0 && !post) return fail(NIP_ERROR_NULLPOINTER, "stream: NULL rows for a push that emits");
+  return 0;
+}
+int flush_check(const nipamd_stream* s, const void* post) {
+  if (!s) return fail(NIP_ERROR_NULLPOINTER, "stream: NULL stream");
+  if (s->pending > 0 && !post) return fail(NIP_ERROR_NULLPOINTER, "stream: NULL rows for a flush that emits");
+  return 0;
+}
+
+// T new steps (T = 0: the flush) as launches of at most kStreamChunk steps
+int stream_run(nipamd_stream* s, const int32_t* d_obs, int T, double* d_post, double* d_ll, uint32_t* d_status,
+               void* stream) {
+  nipamd::StreamArgs a = s->a;
+  if (int rc = stream_tables(s, a)) return rc;
+  const long ocols = s->obs_vars.empty() ? 1 : (long)s->obs_vars.size();
+  const long rows = T > 0 ? rows_of_push(s, T) : s->pending;
+  a.obs_bstride = (long)T * ocols;
+  a.obs_tstride = (int)ocols;
+  a.post_bstride = rows * s->width;
+  a.ll = d_ll; a.status = d_status;
+  long done = 0;
+  for (int c0 = 0; c0 < std::max(T, 1); c0 += nipamd::kStreamChunk) {
+    a.T_new = std::min(nipamd::kStreamChunk, T - c0);
+    a.final = T == 0;
+    a.n = s->n; a.pending = s->pending;
+    a.E = a.final ? s->pending : std::max(0, s->pending + a.T_new - s->lag);
+    a.obs = d_obs ? d_obs + c0 * ocols : nullptr;
+    a.post = d_post ? d_post + done * s->width : nullptr;
+    if (int rc = nipamd::chain_stream_launch(a, (hipStream_t)stream)) return launch_fail(rc, "chain_stream_kernel");
+    done += a.E;
+    s->n += a.T_new;
+    s->pending = a.final ? 0 : (int)std::min<long>(s->n, s->lag);
+  }
+  if (T == 0) s->flushed = true;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nipamd_stream_open(nipamd_model* mm, int n_obs, const int* obs_vars, int n_query, const int* query, int B,
+                       int lag, nipamd_stream** out) {
+  nipamd_stream* s = new nipamd_stream();
+  if (int rc = stream_check(mm, n_obs, obs_vars, n_query, query, B, lag, out, *s)) { delete s; return rc; }
+  // only now the per-sequence state: base and head [B][NP], the ll's two mantissas and exponent, first dead
+  // step, status, ring [B][lag][ncol]
+  const size_t NP = (size_t)nipamd::chain_stream_np(s->a.N), nb = (size_t)B;
+  const size_t ring = nb * (size_t)lag * (size_t)s->a.ncol;
+  const size_t bytes = 2 * nb * NP * sizeof(double) + nb * (2 * sizeof(double) + 2 * sizeof(long) + sizeof(unsigned)) +
+                       ring * sizeof(int);
+  int rc = ensure_device(mm);
+  if (!rc && hipMalloc(&s->state, bytes) != hipSuccess)
+    rc = fail(NIPAMD_ERROR_DEVICE, "stream: device allocation of " + std::to_string(bytes) + " bytes failed");
+  if (!rc) {
+    nipamd::StreamArgs& a = s->a;
+    a.base = static_cast<double*>(s->state);
+    a.head = a.base + nb * NP;
+    a.snum = a.head + nb * NP;
+    a.sden = a.snum + nb;
+    a.sexp = reinterpret_cast<long*>(a.sden + nb);
+    a.sdead = a.sexp + nb;
+    a.sstatus = reinterpret_cast<unsigned*>(a.sdead + nb);
+    a.ring = reinterpret_cast<int*>(a.sstatus + nb);
+    rc = stream_reset(s, nullptr);
+    // the first push may come on any HIP stream
+    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(NIPAMD_ERROR_DEVICE, "stream: initialisation failed");
+  }
+  if (rc) { (void)hipFree(s->state); delete s; return rc; }
+  *out = s;
+  return 0;
+}
+
+int nipamd_stream_push(nipamd_stream* s, const int32_t* d_obs, int T, double* d_post, double* d_ll,
+                       uint32_t* d_status, void* stream) {
+  if (int rc = push_check(s, d_obs, T, d_post)) return rc;
+  return stream_run(s, d_obs, T, d_post, d_ll, d_status, stream);
+}
+
+int nipamd_stream_flush(nipamd_stream* s, double* d_post, double* d_ll, uint32_t* d_status, void* stream) {
+  if (int rc = flush_check(s, d_post)) return rc;
+  return stream_run(s, nullptr, 0, d_post, d_ll, d_status, stream);
+}
+
+int nipamd_stream_reset(nipamd_stream* s, void* stream) {
+  if (!s) return fail(NIP_ERROR_NULLPOINTER, "stream: NULL stream");
+  return stream_reset(s, stream);
+}
+
+int nipamd_stream_pending(const nipamd_stream* s) { return s ? s->pending : -1; }
+
+long nipamd_stream_steps(const nipamd_stream* s) { return s ? s->n : -1; }
+
+void nipamd_stream_free(nipamd_stream* s) {
+  if (!s) return;
+  (void)hipFree(s->state);
+  delete s;
+}
+
+int nipamd_stream_push_host(nipamd_stream* s, const int32_t* obs, int T, double* post, double* ll, uint32_t* status) {
+  if (int rc = push_check(s, obs, T, post)) return rc;
+  const size_t nob = (size_t)s->B * T * s->obs_vars.size();
+  const size_t npo = (size_t)s->B * rows_of_push(s, T) * s->width;
+  return host_call(s->obs_vars.empty() ? nullptr : obs, nob, npo ? post : nullptr, npo, false, ll, status, (size_t)s->B,
+                   [&](int32_t* d_obs, double* d_post, double* d_ll, uint32_t* d_st) {
+                     return stream_run(s, d_obs, T, d_post, d_ll, d_st, nullptr);
+                   });
+}
+
+int nipamd_stream_flush_host(nipamd_stream* s, double* post, double* ll, uint32_t* status) {
+  if (int rc = flush_check(s, post)) return rc;
+  const size_t npo = (size_t)s->B * s->pending * s->width;
+  return host_call((const int32_t*)nullptr, 0, npo ? post : nullptr, npo, false, ll, status, (size_t)s->B,
+                   [&](int32_t*, double* d_post, double* d_ll, uint32_t* d_st) {
+                     return stream_run(s, nullptr, 0, d_post, d_ll, d_st, nullptr);
+                   });
+}
+
+}  // extern "C"

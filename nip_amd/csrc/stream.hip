@@ -1,0 +1,407 @@
+// stream.hip -- online inference over an interface chain: resumable filtering
+// and fixed-lag smoothing, batched over sequences that advance in lockstep
+// (nipamd_stream_*, engine_stream.cpp).
+//
+// The chain plan's forward recursion enters the start of a
+// sequence only through alpha_{-1} = prior, so a forward message kept on the
+// device between calls resumes it at any step.  Per sequence the state holds
+//
+//   head  = alpha^_{n-1}   n = the steps consumed so far
+//   base  = alpha^_{s-1}   s = n - pending, the oldest step whose row is still owed
+//   the ll's two running products (below), status, the first step without mass,
+//   and the raw codes of steps s .. n-1
+//
+// and one launch consumes T_new <= kStreamChunk new steps.  With lag L, row t
+// is the marginal of the interface at step t given y_0 .. y_{t+L} (a flush:
+// .. y_{n-1}); it is emitted by the launch that consumes step t + L:
+//
+//   one step      u = A^T alpha^,  m1 = sum u s_all,  a = u o e_t,  m2 = sum a,
+//                 alpha^ = a / m2,  ll += log m2 - log m1      (m2 = 0: dead from t on)
+//                 -- the ll as chain_wide_kernel carries it: the products of the m2 and of
+//                 the m1 as a mantissa in [0.5, 1) each and one exponent sum, multiplied
+//                 up step by step in the state (two multiplies and two frexp per step
+//                 instead of two logarithms); the ll written out,
+//                 log num - log den + ex ln 2, is a function of the state alone
+//   head          one step per new step
+//   row t         base <- one step (alpha^_t again, the same routine: the same bits);
+//                 beta = 1 at the row's endpoint, beta <- A (e_j o beta) for j = endpoint .. t+1,
+//                 rescaled by an exact power of two every step;
+//                 row = normalise(alpha^_t o beta), summed into the queried variables' digits
+//
+// so a row costs L + 2 mat-vecs (one forward step of the head, one of the base,
+// L backward).  Every step of every sequence runs through the same routine and
+// the ll is summed step by step in the state, so rows, ll and status do not
+// depend on how the steps were split into launches or the batch into streams:
+// they are bit-identical.
+//
+// Layout (chain_viterbi_kernel's): NP = 16, 32 or 64 padded states, one NP-lane
+// group per sequence, lane y = state y, 64 / NP sequences per wave, four
+// independent waves per block, no block barrier after the tables are staged.
+// At NP = 16 column y and row y of A stay in registers and both mat-vecs are
+// dpp_row.h's dot_bcast; above that the operand goes through the wave's own
+// LDS row and A / A^T sit in LDS.  The evidence tables and the window's codes
+// (the pending ring, then the new steps), as table rows, are staged in LDS.
+// Every cross-lane sum starts from a materialised value (row_sum).
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+
+#include "chain_kernels.h"
+#include "dpp_row.h"
+#include "store_pol.h"
+
+namespace nipamd {
+
+namespace {
+
+constexpr int kStrWaves = 4;
+
+__host__ __device__ constexpr int str_np(int N) { return N <= 16 ? 16 : N <= 32 ? 32 : 64; }
+
+__device__ __forceinline__ void wave_lds_sync() {
+  // LDS operations of one wave complete in issue order: the wave's own rows
+  // need no barrier, only the compiler kept from reordering the accesses
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Sum / maximum over the NP lanes of a group, the same bits in every lane (each
+// level pairs lanes whose partial results are equal).
+template <int NP>
+__device__ __forceinline__ double group_sum(double x) {
+  x = row_sum(x);
+  if constexpr (NP >= 32) x += __shfl_xor(x, 16, 64);
+  if constexpr (NP == 64) x += __shfl_xor(x, 32, 64);
+  return x;
+}
+template <int NP>
+__device__ __forceinline__ double group_max(double x) {
+  x = fmax(x, row_ror<8>(x));
+  x = fmax(x, row_ror<4>(x));
+  x = fmax(x, row_ror<2>(x));
+  x = fmax(x, row_ror<1>(x));
+  if constexpr (NP >= 32) x = fmax(x, __shfl_xor(x, 16, 64));
+  if constexpr (NP == 64) x = fmax(x, __shfl_xor(x, 32, 64));
+  return x;
+}
+
+// sum_k v[lane k of the group] c_k for this lane: c = this lane's 16 coefficients
+// in registers (NP = 16), or column `y` of the LDS image Al [k][NP] above that,
+// v passing through the wave's LDS row xch.  A fixed k order.
+template <int NP>
+__device__ __forceinline__ double matvec(double v, const double (&c)[16], const double* Al, double* xch, int lane,
+                                         int gbase, int y) {
+  if constexpr (NP == 16) {
+    return dot_bcast(v, c);
+  } else {
+    xch[lane] = v;
+    wave_lds_sync();
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < NP; k += 4) {
+      a0 = fma(xch[gbase + k], Al[k * NP + y], a0);
+      a1 = fma(xch[gbase + k + 1], Al[(k + 1) * NP + y], a1);
+      a2 = fma(xch[gbase + k + 2], Al[(k + 2) * NP + y], a2);
+      a3 = fma(xch[gbase + k + 3], Al[(k + 3) * NP + y], a3);
+    }
+    wave_lds_sync();
+    return (a0 + a1) + (a2 + a3);
+  }
+}
+
+// the running totals of one sequence (the same values in every lane of its group)
+struct Totals {
+  double num, den;   // mantissas in [0.5, 1) of the products of the m2 and of the m1
+  long ex;           // the products' exponents, num's minus den's
+  unsigned status;
+  long dead;      // the first step without mass, kStreamAlive while there is none
+};
+
+// One forward step at step t: al = alpha^_{t-1} -> alpha^_t under the evidence e.
+// LL: the head's step, which also carries the totals.
+template <int NP, bool LL>
+__device__ __forceinline__ double fwd_step(double al, double e, double sall, const double (&Ac)[16], const double* Af,
+                                           double* xch, int lane, int gbase, int y, long t, Totals& tot) {
+  const double u = matvec<NP>(al, Ac, Af, xch, lane, gbase, y);
+  const double a = u * e;
+  const double m2 = group_sum<NP>(a);
+  const bool ok = m2 > 0.0;
+  if constexpr (LL) {
+    const double m1 = group_sum<NP>(u * sall);
+    if (ok) {
+      int e2 = 0, e1 = 0;
+      tot.num = frexp(tot.num * m2, &e2);
+      tot.den = frexp(tot.den * m1, &e1);
+      tot.ex += e2 - e1;
+    } else {
+      if (tot.dead == kStreamAlive) tot.dead = t;
+      tot.status |= 1u;
+    }
+  }
+  return ok ? a / m2 : 0.0;
+}
+
+template <int NP, int NC>
+__global__ __launch_bounds__(kStrWaves * 64) void chain_stream_kernel(StreamArgs a) {
+  constexpr int G = 64 / NP;
+  constexpr int NCA = NC > 0 ? NC : 1;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // [rows][NP] tables, ebase [NP], A and A^T [NP][NP] (NP > 16), [waves][64] exchange rows,
+  // then the waves' codes [G][lag + kStreamChunk][NC] (int)
+  double* tabs = reinterpret_cast<double*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int row0[NCA], rows = 0;
+#pragma unroll
+  for (int k = 0; k < NC; k++) {
+    row0[k] = rows;
+    const int n = (a.M[k] + 2) * NP;
+    for (int i = tid; i < n; i += kStrWaves * 64) tabs[rows * NP + i] = a.tab[k][(i / NP) * 64 + (i % NP)];
+    rows += a.M[k] + 2;
+  }
+  double* eb = tabs + rows * NP;
+  if (tid < NP) eb[tid] = a.ebase[tid];
+  double* Af = eb + NP;                                    // Af[x][y] = A[x][y]
+  double* Ab = Af + (NP > 16 ? NP * NP : 0);               // Ab[y][x] = A[x][y]
+  if constexpr (NP > 16) {
+    for (int i = tid; i < NP * NP; i += kStrWaves * 64) {
+      const double v = a.A[(i / NP) * 64 + (i % NP)];
+      Af[i] = v;
+      Ab[(i % NP) * NP + (i / NP)] = v;
+    }
+  }
+  double* xch0 = Ab + (NP > 16 ? NP * NP : 0);
+  double* xch = xch0 + wave * 64;
+  const int Wmax = a.lag + kStreamChunk;
+  int* codes = reinterpret_cast<int*>(xch0 + kStrWaves * 64) + wave * (G * Wmax * NC);
+  __syncthreads();
+
+  const int grp = lane / NP, y = lane % NP, gbase = grp * NP;
+  const long gw = (long)blockIdx.x * kStrWaves + wave;     // the wave's sequences: gw G .. gw G + G - 1
+  if (gw * G >= a.B) return;
+  const long b = gw * G + grp;
+  const bool live = b < a.B;
+  const long bl = live ? b : a.B - 1;
+
+  const int L = a.lag, P = a.pending, Tn = a.T_new, W = P + Tn;
+  const long s0 = a.n - P;                                 // the step of window index 0
+
+  // the window's codes as table rows: the ring's pending steps, then the new ones
+  if constexpr (NC > 0) {
+    for (int i = lane; i < G * W * NC; i += 64) {
+      const int k = i % NC, w = (i / NC) % W, g = i / (NC * W);
+      long bb = gw * G + g;
+      bb = bb < a.B ? bb : a.B - 1;
+      int M = 0, r0 = 0, col = 0;
+#pragma unroll
+      for (int kk = 0; kk < NC; kk++)
+        if (k == kk) { M = a.M[kk]; r0 = row0[kk]; col = a.col[kk]; }
+      int raw;
+      if (w < P) raw = a.ring[(bb * L + (s0 + w) % L) * NC + k];
+      else raw = a.obs[bb * a.obs_bstride + (long)(w - P) * a.obs_tstride + col];
+      codes[i] = r0 + (raw < 0 ? M : (raw < M ? raw : M + 1));
+    }
+    wave_lds_sync();
+  }
+  auto evid = [&](int w) {
+    double e = eb[y];
+#pragma unroll
+    for (int k = 0; k < NC; k++) e *= tabs[codes[(grp * W + w) * NC + k] * NP + y];
+    return e;
+  };
+
+  double Ac[16], Ar[16];                                   // column y and row y of A (NP = 16)
+  if constexpr (NP == 16) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      Ac[k] = a.A[k * 64 + y];
+      Ar[k] = a.A[y * 64 + k];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++) Ac[k] = Ar[k] = 0.0;
+  }
+  const double sall = a.sall[y];
+
+  Totals tot{a.snum[bl], a.sden[bl], a.sexp[bl], a.sstatus[bl], a.sdead[bl]};
+  Totals none{};                                           // the base's steps carry no totals
+  double hd = a.head[bl * NP + y];
+  const int width = a.post_tstride;
+  double* prow = a.post ? a.post + bl * a.post_bstride : nullptr;
+
+  // row = normalise(p) (norm; else p as it is: alpha^ is normalised), all zeros
+  // where the sequence has no mass at the row's endpoint; the interface state
+  // itself, or the queried variables' digit sums
+  auto emit = [&](double p, bool norm, bool zero, int r) {
+    double v = p;
+    if (norm) {
+      const double s = group_sum<NP>(p);
+      v = s > 0.0 ? p / s : 0.0;
+    }
+    v = zero ? 0.0 : v;
+    double* dst = prow + (long)r * width;
+    if (a.nq == 0) {
+      if (live && y < a.N) store_pol<NIPAMD_POST_NT != 0>(dst + y, v);
+      return;
+    }
+    xch[lane] = v;
+    wave_lds_sync();
+    for (int c = y; c < width; c += NP) {
+      int j = 0, d = c;
+      while (j < a.nq - 1 && d >= a.qcard[j]) { d -= a.qcard[j]; j++; }
+      const int qs = a.qstride[j], qc = a.qcard[j];
+      double acc = 0.0;
+      for (int x = 0; x < a.N; x++) acc += (x / qs) % qc == d ? xch[gbase + x] : 0.0;
+      if (live) store_pol<NIPAMD_POST_NT != 0>(dst + c, acc);
+    }
+    wave_lds_sync();
+  };
+
+  if (L == 0) {
+    // filtering: the row of step t is alpha^_t itself
+    for (int w = 0; w < Tn; w++) {
+      hd = fwd_step<NP, true>(hd, evid(w), sall, Ac, Af, xch, lane, gbase, y, s0 + w, tot);
+      emit(hd, false, tot.dead != kStreamAlive, w);
+    }
+  } else {
+    for (int w = P; w < W; w++)
+      hd = fwd_step<NP, true>(hd, evid(w), sall, Ac, Af, xch, lane, gbase, y, s0 + w, tot);
+    double bs = a.base[bl * NP + y];
+    for (int r = 0; r < a.E; r++) {                        // row t = s0 + r
+      bs = fwd_step<NP, false>(bs, evid(r), sall, Ac, Af, xch, lane, gbase, y, s0 + r, none);
+      const int endw = a.final ? W - 1 : r + L;            // the row's endpoint min(t + L, n_end - 1)
+      double beta = 1.0;
+      for (int j = endw; j > r; j--) {
+        beta = matvec<NP>(evid(j) * beta, Ar, Ab, xch, lane, gbase, y);
+        int ex = 0;
+        (void)frexp(group_max<NP>(beta), &ex);            // 0 for a maximum of 0
+        beta = ldexp(beta, -ex);
+      }
+      emit(bs * beta, true, s0 + endw >= tot.dead, r);
+    }
+    if (live) a.base[b * NP + y] = bs;
+  }
+
+  // the state, and the new steps that stay pending into the ring
+  if (live) {
+    a.head[b * NP + y] = hd;
+    if (y == 0) {
+      a.snum[b] = tot.num;
+      a.sden[b] = tot.den;
+      a.sexp[b] = tot.ex;
+      a.sstatus[b] = tot.status;
+      a.sdead[b] = tot.dead;
+      if (a.ll)
+        a.ll[b] = tot.dead != kStreamAlive
+                      ? -DBL_MAX
+                      : log(tot.num) - log(tot.den) + (double)tot.ex * 0.69314718055994530942;
+      if (a.status) a.status[b] = tot.status;
+    }
+  }
+  if constexpr (NC > 0) {
+    const long nend = a.n + Tn;
+    const long keep = nend < L ? nend : L;                 // pending after this launch
+    const long t0 = a.n > nend - keep ? a.n : nend - keep; // the first new step that stays
+    const int cnt = (int)(nend - t0);
+    for (int i = lane; i < G * cnt * NC; i += 64) {
+      const int k = i % NC, q = (i / NC) % cnt, g = i / (NC * cnt);
+      const long bb = gw * G + g;
+      if (bb >= a.B) continue;
+      int col = 0;
+#pragma unroll
+      for (int kk = 0; kk < NC; kk++)
+        if (k == kk) col = a.col[kk];
+      const long t = t0 + q;
+      a.ring[(bb * L + t % L) * NC + k] = a.obs[bb * a.obs_bstride + (t - a.n) * a.obs_tstride + col];
+    }
+  }
+}
+
+__global__ void chain_stream_init_kernel(StreamArgs a, const double* pi64, int NP) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.B * NP) {
+    const double v = pi64[i % NP];
+    a.base[i] = v;
+    a.head[i] = v;
+  }
+  if (i < a.B) {
+    a.snum[i] = 1.0;
+    a.sden[i] = 1.0;
+    a.sexp[i] = 0;
+    a.sstatus[i] = 0u;
+    a.sdead[i] = kStreamAlive;
+  }
+}
+
+template <int NP, int NC>
+int str_run(const StreamArgs& a, size_t lds, bool launch, hipStream_t stream) {
+  static size_t lds_set[kMaxDevices] = {};
+  if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_stream_kernel<NP, NC>), lds, lds_set))
+    return rc;
+  if (!launch) return 0;
+  const long waves = (a.B + 64 / NP - 1) / (64 / NP);
+  const dim3 grid((unsigned)((waves + kStrWaves - 1) / kStrWaves)), block(kStrWaves * 64);
+  hipLaunchKernelGGL((chain_stream_kernel<NP, NC>), grid, block, lds, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int NP>
+int str_run_np(const StreamArgs& a, size_t lds, bool launch, hipStream_t stream) {
+  switch (a.ncol) {
+    case 0: return str_run<NP, 0>(a, lds, launch, stream);
+    case 1: return str_run<NP, 1>(a, lds, launch, stream);
+    case 2: return str_run<NP, 2>(a, lds, launch, stream);
+    case 3: return str_run<NP, 3>(a, lds, launch, stream);
+    default: return str_run<NP, 4>(a, lds, launch, stream);
+  }
+}
+
+bool str_shape_ok(const StreamArgs& a) {
+  if (a.N < 1 || a.N > 64 || a.ncol < 0 || a.ncol > 4 || a.nq < 0 || a.nq > kViterbiMaxQuery || a.B < 1 ||
+      a.B > 0x7fffffffL || a.lag < 0 || a.lag > kStreamMaxLag)
+    return false;
+  for (int k = 0; k < a.ncol; k++) if (a.M[k] < 1) return false;
+  for (int j = 0; j < a.nq; j++) if (a.qstride[j] < 1 || a.qcard[j] < 1) return false;
+  return true;
+}
+
+int str_dispatch(const StreamArgs& a, bool launch, hipStream_t stream) {
+  const size_t lds = (chain_stream_lds_bytes(a) + 15) & ~(size_t)15;
+  if (a.N <= 16) return str_run_np<16>(a, lds, launch, stream);
+  if (a.N <= 32) return str_run_np<32>(a, lds, launch, stream);
+  return str_run_np<64>(a, lds, launch, stream);
+}
+
+}  // namespace
+
+int chain_stream_np(int N) { return str_np(N); }
+
+size_t chain_stream_lds_bytes(const StreamArgs& a) {
+  const int NP = str_np(a.N), G = 64 / NP;
+  size_t rows = 1;                                         // ebase
+  for (int k = 0; k < a.ncol; k++) rows += (size_t)a.M[k] + 2;
+  const size_t dbl = rows * NP + (NP > 16 ? 2 * (size_t)NP * NP : 0) + kStrWaves * 64;
+  const size_t ints = (size_t)kStrWaves * G * (a.lag + kStreamChunk) * a.ncol;
+  return dbl * sizeof(double) + ints * sizeof(int);
+}
+
+int chain_stream_prepare(const StreamArgs& a) {
+  if (!str_shape_ok(a)) return kLaunchRefused;
+  return str_dispatch(a, false, nullptr);
+}
+
+int chain_stream_launch(const StreamArgs& a, hipStream_t stream) {
+  if (!str_shape_ok(a) || a.T_new < 0 || a.T_new > kStreamChunk || a.pending < 0 || a.pending > a.lag ||
+      a.E < 0 || a.E > a.pending + a.T_new || (a.E > 0 && !a.post))
+    return kLaunchRefused;
+  g_last_kernel = "chain_stream_kernel";
+  return str_dispatch(a, true, stream);
+}
+
+int chain_stream_init_launch(const StreamArgs& a, const double* pi64, hipStream_t stream) {
+  const int NP = str_np(a.N);
+  const long n = a.B * NP;
+  hipLaunchKernelGGL(chain_stream_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a, pi64, NP);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace nipamd
