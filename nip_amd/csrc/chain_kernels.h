@@ -105,16 +105,26 @@ struct ChainFinalize {
   const double* Etab;               // [(M+2)][16]
 };
 
-// wide interface chains (chain_wide.hip): N <= 64 states, up to 4 observed children
-struct WideArgs {
-  const int* obs;        // int32 observations [B][T][n_obs]
+// The raw observation o of a child with M states as a row of its table: the
+// state itself, M = missing (the row sums), M + 1 = out of range (zeros).
+__host__ __device__ __forceinline__ int code_of(int o, int M) { return o < 0 ? M : (o < M ? o : M + 1); }
+
+// The evidence of a request over the wide request tables (engine_dev.cpp
+// ensure_req_tables): what WideArgs, ViterbiArgs and StreamArgs open with
+// (engine_internal.h set_obs_view / set_cols fill it).
+struct EvidenceArgs {
+  const int* obs;        // int32 observations [B][T][n_obs] (StreamArgs: the new steps [B][T_new ..][n_obs])
   long obs_bstride;      // elements between sequences
   int obs_tstride;       // elements between time steps
-  int ncol;              // observed children used (columns)
+  int ncol;              // observed columns (children, or the interface variable itself)
   int col[4];            // their columns in obs
   int M[4];              // their cardinalities
   const double* tab[4];  // [(M+2)][64] per column: E, then the row sums, then 0
   const double* ebase;   // [64] product of the unobserved children's row sums
+};
+
+// wide interface chains (chain_wide.hip): N <= 64 states, up to 4 observed children
+struct WideArgs : EvidenceArgs {
   long B;
   int T, H, N;
   const double* A;       // [64][64]
@@ -216,15 +226,7 @@ int derive_launch(const DeriveArgs& a, hipStream_t stream);
 // variable: one column, qstride 1, qcard N); -1 everywhere, logp = -DBL_MAX
 // and status 1 for a sequence without mass.
 constexpr int kViterbiMaxQuery = 8;
-struct ViterbiArgs {
-  const int* obs;        // int32 observations [B][T][n_obs]
-  long obs_bstride;      // elements between sequences
-  int obs_tstride;       // elements between time steps
-  int ncol;              // observed columns
-  int col[4];            // their columns in obs
-  int M[4];              // their cardinalities
-  const double* tab[4];  // [(M+2)][64] per column: E, then the row sums, then 0
-  const double* ebase;   // [64] product of the unobserved children's row sums
+struct ViterbiArgs : EvidenceArgs {
   const double* A;       // [64][64]
   const double* u0;      // [64] pi A
   long B;
@@ -254,15 +256,7 @@ int chain_viterbi_launch(const ViterbiArgs& a, hipStream_t stream);
 constexpr int kStreamChunk = 64;
 constexpr int kStreamMaxLag = 64;
 constexpr long kStreamAlive = 0x7fffffffffffffffL;   // "first step without mass" of a live sequence
-struct StreamArgs {
-  const int* obs;        // int32 observations of the new steps [B][T_new ..][n_obs]
-  long obs_bstride;      // elements between sequences
-  int obs_tstride;       // elements between time steps
-  int ncol;              // observed columns
-  int col[4];            // their columns in obs
-  int M[4];              // their cardinalities
-  const double* tab[4];  // [(M+2)][64] per column: E, then the row sums, then 0
-  const double* ebase;   // [64] product of the unobserved children's row sums
+struct StreamArgs : EvidenceArgs {
   const double* A;       // [64][64]
   const double* sall;    // [64] product of every child's row sums
   long B;

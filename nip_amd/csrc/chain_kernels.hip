@@ -206,7 +206,6 @@ void chain_kernel(ChainArgs a) {
   // --- stage the evidence table and this block's observation codes in LDS
   for (int i = tid; i < (a.M + 2) * 16; i += kThreads) Et[i] = a.Etab[i];
   const int nseq = (int)((a.B - b0) < kChainsPerBlock ? (a.B - b0) : kChainsPerBlock);
-  auto code_of = [&](int o) -> int { return o < 0 ? a.M : (o < a.M ? o : a.M + 1); };
   for (int i = tid; i < kChainsPerBlock * Tr; i += kThreads) codes[i] = (uint8_t)a.M;  // missing / guard
   if (ESTEP)
     for (int i = tid; i < kChainsPerBlock * 2 * (a.M + 2) * 16; i += kThreads) Htab[i] = 0.0;
@@ -224,8 +223,8 @@ void chain_kernel(ChainArgs a) {
         const int i4 = i0 + k * kThreads;
         if (i4 < n4) {
           const int i = i4 << 2, c = i / T, t = i - c * T;
-          const uint32_t packed = (uint32_t)code_of(r[k].x) | ((uint32_t)code_of(r[k].y) << 8) |
-                                  ((uint32_t)code_of(r[k].z) << 16) | ((uint32_t)code_of(r[k].w) << 24);
+          const uint32_t packed = (uint32_t)code_of(r[k].x, a.M) | ((uint32_t)code_of(r[k].y, a.M) << 8) |
+                                  ((uint32_t)code_of(r[k].z, a.M) << 16) | ((uint32_t)code_of(r[k].w, a.M) << 24);
           *reinterpret_cast<uint32_t*>(codes + c * Tr + kGuard + t) = packed;
         }
       }
@@ -234,7 +233,7 @@ void chain_kernel(ChainArgs a) {
     for (int i = tid; i < nseq * T; i += kThreads) {
       const int c = i / T, t = i - c * T;
       codes[c * Tr + kGuard + t] =
-          (uint8_t)code_of(a.obs[(b0 + c) * a.obs_bstride + (long)t * a.obs_tstride + a.obs_col]);
+          (uint8_t)code_of(a.obs[(b0 + c) * a.obs_bstride + (long)t * a.obs_tstride + a.obs_col], a.M);
     }
   }
 
@@ -834,7 +833,6 @@ void chain_estep16_kernel(ChainArgs a) {
   for (int i = tid; i < R * 16; i += kE16Threads) Et[i] = a.Etab[i];
   const int nseq = (int)((a.B - b0) < kE16Seqs ? (a.B - b0) : kE16Seqs);
   // child k's code: its state, eM[k] missing, eM[k] + 1 out of range (an all-zero row)
-  auto code_of = [&](int k, int o) -> int { return o < 0 ? a.eM[k] : (o < a.eM[k] ? o : a.eM[k] + 1); };
 #pragma unroll
   for (int k = 0; k < NE; k++)
     for (int i = tid; i < kE16Seqs * Tr; i += kE16Threads) codes[(size_t)k * kE16Seqs * Tr + i] = (uint8_t)a.eM[k];
@@ -853,8 +851,9 @@ void chain_estep16_kernel(ChainArgs a) {
         const int i4 = i0 + k * kE16Threads;
         if (i4 < n4) {
           const int i = i4 << 2, c = i / T, t = i - c * T;
-          const uint32_t packed = (uint32_t)code_of(0, r[k].x) | ((uint32_t)code_of(0, r[k].y) << 8) |
-                                  ((uint32_t)code_of(0, r[k].z) << 16) | ((uint32_t)code_of(0, r[k].w) << 24);
+          const uint32_t packed =
+              (uint32_t)code_of(r[k].x, a.eM[0]) | ((uint32_t)code_of(r[k].y, a.eM[0]) << 8) |
+              ((uint32_t)code_of(r[k].z, a.eM[0]) << 16) | ((uint32_t)code_of(r[k].w, a.eM[0]) << 24);
           *reinterpret_cast<uint32_t*>(codes + c * Tr + kGuard + t) = packed;
         }
       }
@@ -865,7 +864,8 @@ void chain_estep16_kernel(ChainArgs a) {
       const int* o = a.obs + (b0 + c) * a.obs_bstride + (long)t * a.obs_tstride;
 #pragma unroll
       for (int k = 0; k < NE; k++)
-        if (a.ecol[k] >= 0) codes[((size_t)k * kE16Seqs + c) * Tr + kGuard + t] = (uint8_t)code_of(k, o[a.ecol[k]]);
+        if (a.ecol[k] >= 0)
+          codes[((size_t)k * kE16Seqs + c) * Tr + kGuard + t] = (uint8_t)code_of(o[a.ecol[k]], a.eM[k]);
     }
   }
   __syncthreads();

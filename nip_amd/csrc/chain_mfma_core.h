@@ -485,7 +485,6 @@ __device__ __forceinline__ void stage_codes(const ChainArgs& a, long b0, int tid
   auto put_et = [&](int i) { Et[(i >> 4) * ESTR + (i & 15)] = a.Etab[i]; };   // row stride ESTR
   const int T = a.T;
   const int nseq = (int)((a.B - b0) < kMSeq ? (a.B - b0) : kMSeq);
-  auto code_of = [&](int o) -> int { return o < 0 ? a.M : (o < a.M ? o : a.M + 1); };
   const bool fast = a.obs && a.obs_tstride == 1 && a.obs_bstride == T && (T & 3) == 0 && nseq == kMSeq;
   if (fast) {
     // contiguous [16][T] int32: every 16-byte load of the first pass issued
@@ -505,8 +504,8 @@ __device__ __forceinline__ void stage_codes(const ChainArgs& a, long b0, int tid
         const int i4 = i0 + k * NT;
         if (i4 < n4) {
           const int i = i4 << 2, cq = i / T, t = i - cq * T;
-          const uint32_t packed = (uint32_t)code_of(r[k].x) | ((uint32_t)code_of(r[k].y) << 8) |
-                                  ((uint32_t)code_of(r[k].z) << 16) | ((uint32_t)code_of(r[k].w) << 24);
+          const uint32_t packed = (uint32_t)code_of(r[k].x, a.M) | ((uint32_t)code_of(r[k].y, a.M) << 8) |
+                                  ((uint32_t)code_of(r[k].z, a.M) << 16) | ((uint32_t)code_of(r[k].w, a.M) << 24);
           *reinterpret_cast<uint32_t*>(codes + cq * Tr + kMG + t) = packed;
         }
       }
@@ -535,7 +534,7 @@ __device__ __forceinline__ void stage_codes(const ChainArgs& a, long b0, int tid
       for (int i = tid; i < nseq * T; i += NT) {
         const int cq = i / T, t = i - cq * T;
         codes[cq * Tr + kMG + t] =
-            (uint8_t)code_of(a.obs[(b0 + cq) * a.obs_bstride + (long)t * a.obs_tstride + a.obs_col]);
+            (uint8_t)code_of(a.obs[(b0 + cq) * a.obs_bstride + (long)t * a.obs_tstride + a.obs_col], a.M);
       }
     }
   }

@@ -683,7 +683,7 @@ void chain_wide4_kernel(WideArgs a) {
       int c = M;                                      // missing / guard
       if (t >= 0 && t < T) {
         const int o = a.obs[b * a.obs_bstride + (long)t * a.obs_tstride + a.col[k]];
-        c = o < 0 ? M : (o < M ? o : M + 1);
+        c = code_of(o, M);
       }
       codes[k * Tr + i] = (uint8_t)c;
     }

@@ -38,7 +38,6 @@ namespace {
 
 constexpr int kMaxN = 64;
 
-__device__ __forceinline__ int code_of(int o, int M) { return o < 0 ? M : (o < M ? o : M + 1); }
 
 // e_t(y) (wide tables: [(M_i + 2)][64] per observed column)
 __device__ __forceinline__ double evidence(const DeriveArgs& a, long b, int t, int y) {

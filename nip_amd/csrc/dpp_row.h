@@ -1,7 +1,8 @@
-// dpp_row.h -- 16-lane DPP row primitives shared by the row-form chain
-// kernels (chain_kernels.hip: the e_step; chain_ckpt.hip: the row-form
-// filters of chain_fb_ckd_kernel).  One 16-lane row holds one chain's 16
-// states, lane y state y.  Included inside an anonymous namespace user.
+// dpp_row.h -- 16-lane DPP row primitives shared by the kernels that keep a
+// chain's states in the lanes of a row: chain_kernels.hip (the e_step and the
+// row-form filters), estep_wide.hip (the broadcast mat-vecs of its filters),
+// and viterbi.hip / stream.hip (through chain_group.h).  One 16-lane row holds
+// 16 states, lane y state y.  Included inside an anonymous namespace user.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,6 +82,15 @@ __device__ __forceinline__ double row_sum(double x) {
   x += row_ror<4>(x);
   x += row_ror<2>(x);
   x += row_ror<1>(x);
+  return x;
+}
+
+// the maximum over the 16 lanes of the row, in every lane
+__device__ __forceinline__ double row_max(double x) {
+  x = fmax(x, row_ror<8>(x));
+  x = fmax(x, row_ror<4>(x));
+  x = fmax(x, row_ror<2>(x));
+  x = fmax(x, row_ror<1>(x));
   return x;
 }
 

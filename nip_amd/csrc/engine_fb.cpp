@@ -360,20 +360,11 @@ long mlss_chunk(int N, int T) {
 // and the evidence route.
 int mlss_check(nipamd_model* mm, const void* obs, int n_obs, const int* obs_vars, int B, int T, int n_query,
                const int* query, const void* path, nipamd::ViterbiArgs& a, Route& r) {
-  if (!mm || !path || (n_obs > 0 && (!obs || !obs_vars)) || (n_query > 0 && !query))
-    return fail(NIP_ERROR_NULLPOINTER, "mlss: NULL model, observations, variables or path");
-  if (B <= 0 || T <= 0 || n_obs < 0 || n_query < 0) return fail(NIP_ERROR_INVALID_ARGUMENT, "mlss: bad arguments");
-  const int nv = (int)mm->m.vars.size();
-  for (int i = 0; i < n_obs; i++)
-    if (obs_vars[i] < 0 || obs_vars[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "mlss: bad observed variable");
-  for (int i = 0; i < n_query; i++)
-    if (query[i] < 0 || query[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "mlss: bad query variable");
+  if (int rc = check_var_lists("mlss", mm, !path || (n_obs > 0 && !obs), "NULL model, observations, variables or path",
+                               B <= 0 || T <= 0, "bad arguments", n_obs, obs_vars, n_query, query))
+    return rc;
+  if (int rc = chain_scope(mm, "mlss", "the most likely state sequence", "")) return rc;
   const auto& P = mm->m.chain;
-  if (mm->engine == NIPAMD_ENGINE_JTREE)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the engine is set to NIPAMD_ENGINE_JTREE; the most likely state "
-                                          "sequence runs on the interface-chain plan only");
-  if (!P.valid)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: model slice is not an interface chain (no chain plan; see DESIGN.md)");
   // the variables of interest are the interface, all of it and nothing else
   bool is_if = true;
   if (!P.joint) {
@@ -384,15 +375,8 @@ int mlss_check(nipamd_model* mm, const void* obs, int n_obs, const int* obs_vars
       return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the joint interface has " + std::to_string(P.jcur.size()) +
                                                 " variables; the path holds at most " +
                                                 std::to_string(nipamd::kViterbiMaxQuery) + " columns");
-    is_if = n_query == (int)P.jcur.size();
-    for (int j = 0; is_if && j < n_query; j++) {
-      int k = -1, stride = 1;
-      for (size_t i = 0; i < P.jcur.size(); i++) if (P.jcur[i] == query[j]) k = (int)i;
-      for (int i = 0; i < j; i++) is_if &= query[i] != query[j];
-      if (k < 0) { is_if = false; break; }
-      for (int i = 0; i < k; i++) stride *= mm->m.vars[P.jcur[i]].card;
-      a.qstride[j] = stride; a.qcard[j] = mm->m.vars[query[j]].card;
-    }
+    int width = 0;
+    is_if = n_query == (int)P.jcur.size() && interface_digits(mm, n_query, query, a.qstride, a.qcard, &width);
     a.nq = n_query;
   }
   if (!is_if)

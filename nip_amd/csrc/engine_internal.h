@@ -170,6 +170,11 @@ int upload(DevState* d, double** dst, const V& v) {
 int query_kind(const ChainPlan& P, int v);
 int route_request(const nipamd_model* mm, int n_obs, const int* obs_vars, int n_query, const int* query,
                   Route& r, std::string& why);
+// the verdicts mlss and the streams share: arguments, scope, a joint interface's query
+int check_var_lists(const std::string& what, const nipamd_model* mm, bool null, const char* null_msg, bool bad,
+                    const std::string& bad_msg, int n_obs, const int* obs_vars, int n_query, const int* query);
+int chain_scope(const nipamd_model* mm, const std::string& what, const char* subject, const char* no_plan);
+bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int* qstride, int* qcard, int* width);
 bool chain_proper(const ChainPlan& P);
 bool estep16_sparse_ok(const ChainPlan& P, int ne);
 bool ckw_sparse_ok(const ChainPlan& P, const Route& r, const bool (&seen)[4]);

@@ -56,6 +56,56 @@ int route_request(const nipamd_model* mm, int n_obs, const int* obs_vars, int n_
   return 1;
 }
 
+// The argument verdict of a chain-plan entry point (`what`: "mlss", "stream"),
+// in the order all of them give it: a NULL model or variable list, or the
+// caller's own `null` -> NIP_ERROR_NULLPOINTER; a negative count, or the
+// caller's own `bad` -> NIP_ERROR_INVALID_ARGUMENT; then every variable index
+// against the model.  null_msg / bad_msg: the entry point's wording.
+int check_var_lists(const std::string& what, const nipamd_model* mm, bool null, const char* null_msg, bool bad,
+                    const std::string& bad_msg, int n_obs, const int* obs_vars, int n_query, const int* query) {
+  if (!mm || null || (n_obs > 0 && !obs_vars) || (n_query > 0 && !query))
+    return fail(NIP_ERROR_NULLPOINTER, what + ": " + null_msg);
+  if (bad || n_obs < 0 || n_query < 0) return fail(NIP_ERROR_INVALID_ARGUMENT, what + ": " + bad_msg);
+  const int nv = (int)mm->m.vars.size();
+  for (int i = 0; i < n_obs; i++)
+    if (obs_vars[i] < 0 || obs_vars[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, what + ": bad observed variable");
+  for (int i = 0; i < n_query; i++)
+    if (query[i] < 0 || query[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, what + ": bad query variable");
+  return 0;
+}
+
+// The scope of an entry point that runs on the interface-chain plan only
+// (`subject` runs ...; no_plan: what else the refusal of a model without a
+// chain plan says).
+int chain_scope(const nipamd_model* mm, const std::string& what, const char* subject, const char* no_plan) {
+  if (mm->engine == NIPAMD_ENGINE_JTREE)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": the engine is set to NIPAMD_ENGINE_JTREE; " + subject +
+                                              " runs on the interface-chain plan only");
+  if (!mm->m.chain.valid)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": model slice is not an interface chain (no chain plan; " + no_plan +
+                                              "see DESIGN.md)");
+  return 0;
+}
+
+// query [n_query] as digits of a joint interface's state (the first variable
+// fastest): false unless it lists distinct current-slice interface variables.
+// qstride / qcard [n_query]: variable j is (state / qstride[j]) % qcard[j];
+// *width: the sum of their cardinalities.
+bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int* qstride, int* qcard, int* width) {
+  const auto& P = mm->m.chain;
+  *width = 0;
+  for (int j = 0; j < n_query; j++) {
+    int k = -1, stride = 1;
+    for (size_t i = 0; i < P.jcur.size(); i++) if (P.jcur[i] == query[j]) k = (int)i;
+    for (int i = 0; i < j; i++) if (query[i] == query[j]) return false;
+    if (k < 0) return false;
+    for (int i = 0; i < k; i++) stride *= mm->m.vars[P.jcur[i]].card;
+    qstride[j] = stride; qcard[j] = mm->m.vars[query[j]].card;
+    *width += qcard[j];
+  }
+  return true;
+}
+
 // The chain's transition rows and every child's rows sum to 1 within 1e-15
 // (normalised CPTs; every m_step's output): the reference's per-step
 // log m2 - log m1 then telescope to log P(obs) (m1_t is the previous step's

@@ -32,23 +32,15 @@ static_assert(NIPAMD_STREAM_CHUNK == nipamd::kStreamChunk && NIPAMD_STREAM_MAX_L
 // the query digits and the shape of s.
 int stream_check(nipamd_model* mm, int n_obs, const int* obs_vars, int n_query, const int* query, int B, int lag,
                  nipamd_stream** out, nipamd_stream& s) {
-  if (!mm || !out || (n_obs > 0 && !obs_vars) || (n_query > 0 && !query))
-    return fail(NIP_ERROR_NULLPOINTER, "stream: NULL model, variables or result");
-  if (B < 1 || lag < 0 || lag > NIPAMD_STREAM_MAX_LAG || n_obs < 0 || n_query < 0)
-    return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad arguments (B >= 1, 0 <= lag <= " +
-                                                std::to_string(NIPAMD_STREAM_MAX_LAG) + ")");
-  const int nv = (int)mm->m.vars.size();
-  for (int i = 0; i < n_obs; i++)
-    if (obs_vars[i] < 0 || obs_vars[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad observed variable");
-  for (int i = 0; i < n_query; i++)
-    if (query[i] < 0 || query[i] >= nv) return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad query variable");
+  if (int rc = check_var_lists("stream", mm, !out, "NULL model, variables or result",
+                               B < 1 || lag < 0 || lag > NIPAMD_STREAM_MAX_LAG,
+                               "bad arguments (B >= 1, 0 <= lag <= " + std::to_string(NIPAMD_STREAM_MAX_LAG) + ")",
+                               n_obs, obs_vars, n_query, query))
+    return rc;
+  if (int rc = chain_scope(mm, "stream", "online inference",
+                           "the operator chain and the general engine have no online form; "))
+    return rc;
   const auto& P = mm->m.chain;
-  if (mm->engine == NIPAMD_ENGINE_JTREE)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: the engine is set to NIPAMD_ENGINE_JTREE; online inference runs "
-                                          "on the interface-chain plan only");
-  if (!P.valid)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: model slice is not an interface chain (no chain plan; the operator "
-                                          "chain and the general engine have no online form; see DESIGN.md)");
   std::string why;
   if (!route_request(mm, n_obs, obs_vars, 0, nullptr, s.r, why)) return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: " + why);
   // the query: distinct current-slice interface variables, at least one
@@ -59,17 +51,8 @@ int stream_check(nipamd_model* mm, int n_obs, const int* obs_vars, int n_query, 
     a.nq = 0;
     s.width = P.N;
   } else {
-    is_if &= n_query <= nipamd::kViterbiMaxQuery;
-    s.width = 0;
-    for (int j = 0; is_if && j < n_query; j++) {
-      int k = -1, stride = 1;
-      for (size_t i = 0; i < P.jcur.size(); i++) if (P.jcur[i] == query[j]) k = (int)i;
-      for (int i = 0; i < j; i++) is_if &= query[i] != query[j];
-      if (k < 0) { is_if = false; break; }
-      for (int i = 0; i < k; i++) stride *= mm->m.vars[P.jcur[i]].card;
-      a.qstride[j] = stride; a.qcard[j] = mm->m.vars[query[j]].card;
-      s.width += a.qcard[j];
-    }
+    is_if = is_if && n_query <= nipamd::kViterbiMaxQuery &&
+            interface_digits(mm, n_query, query, a.qstride, a.qcard, &s.width);
     a.nq = n_query;
   }
   if (!is_if)

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
       for (int k = 0; k < 4; k++) {
         const bool in = active && t0 + k >= 0 && t0 + k < T;
         const int o = in ? r.v[q][k] : -1;
-        const int cd = o < 0 ? M : (o < M ? o : M + 1);
+        const int cd = code_of(o, M);
         x |= (unsigned)cd << (8 * k);
       }
       w[q] = x;

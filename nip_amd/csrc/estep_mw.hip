@@ -485,7 +485,7 @@ __device__ __forceinline__ void epartner(const EMwArgs& a, double* ring, int* re
   };
   auto ev_row = [&](int c, int o) {                  // this lane's two states of column c's row for raw code o
     const int M = a.ncol > 0 ? a.M[c] : 0;
-    const int r = o < 0 ? M : (o < M ? o : M + 1);
+    const int r = code_of(o, M);
     return *reinterpret_cast<const v2d*>(tab + a.tab_off[c] / NP * NPS + r * NPS + 2 * s);
   };
 

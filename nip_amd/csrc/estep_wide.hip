@@ -102,7 +102,6 @@ __device__ __forceinline__ double recip(double c) {
 }
 
 // child c's code at step t: its state, M missing, M + 1 out of range
-__device__ __forceinline__ int code_of(int o, int M) { return o < 0 ? M : (o < M ? o : M + 1); }
 
 // the step's evidence e_t(y): the unobserved children's row sums times each
 // observed child's table row
@@ -555,7 +554,7 @@ __device__ __forceinline__ double op_leaf_e(const OpWideArgs& a, const int32_t* 
   double e = 1.0;
   for (int j = 0; j < a.nleaf; j++) {
     const int v = o[a.lcol[j]], M = a.lcard[j];
-    const int r = v < 0 ? M : (v < M ? v : M + 1);
+    const int r = code_of(v, M);
     e *= a.ltab[a.loff[j] + r * a.K + y];
   }
   return e;
@@ -666,7 +665,7 @@ __global__ __launch_bounds__(MsgCfg<NP>::waves * 64) __attribute__((amdgpu_waves
 #pragma unroll
       for (int k = 0; k < kOpMsgChunk; k++) {
         ev[k] |= v[k] >= 0;
-        const int r = v[k] < 0 ? M : (v[k] < M ? v[k] : M + 1);
+        const int r = code_of(v[k], M);
         e[k] *= in[k] ? lt[r * K] : 1.0;
       }
     }
@@ -823,7 +822,7 @@ __device__ __forceinline__ int op_key(const OpWideArgs& a, const int32_t* o) {
   int k = (op_code(a, o) & (kOpEv - 1)) << a.Lbits;
   for (int j = 0; j < a.nleaf; j++) {
     const int v = o[a.lcol[j]], M = a.lcard[j];
-    k |= (v < 0 ? M : (v < M ? v : M + 1)) << a.lsh[j];
+    k |= code_of(v, M) << a.lsh[j];
   }
   return k;
 }

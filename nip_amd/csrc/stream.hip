@@ -34,9 +34,8 @@
 // depend on how the steps were split into launches or the batch into streams:
 // they are bit-identical.
 //
-// Layout (chain_viterbi_kernel's): NP = 16, 32 or 64 padded states, one NP-lane
-// group per sequence, lane y = state y, 64 / NP sequences per wave, four
-// independent waves per block, no block barrier after the tables are staged.
+// Layout: chain_group.h's lane groups (NP = 16, 32 or 64 padded states, one
+// NP-lane group per sequence), no block barrier after the tables are staged.
 // At NP = 16 column y and row y of A stay in registers and both mat-vecs are
 // dpp_row.h's dot_bcast; above that the operand goes through the wave's own
 // LDS row and A / A^T sit in LDS.  The evidence tables and the window's codes
@@ -46,44 +45,12 @@
 
 #include <cfloat>
 
-#include "chain_kernels.h"
-#include "dpp_row.h"
+#include "chain_group.h"
 #include "store_pol.h"
 
 namespace nipamd {
 
 namespace {
-
-constexpr int kStrWaves = 4;
-
-__host__ __device__ constexpr int str_np(int N) { return N <= 16 ? 16 : N <= 32 ? 32 : 64; }
-
-__device__ __forceinline__ void wave_lds_sync() {
-  // LDS operations of one wave complete in issue order: the wave's own rows
-  // need no barrier, only the compiler kept from reordering the accesses
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// Sum / maximum over the NP lanes of a group, the same bits in every lane (each
-// level pairs lanes whose partial results are equal).
-template <int NP>
-__device__ __forceinline__ double group_sum(double x) {
-  x = row_sum(x);
-  if constexpr (NP >= 32) x += __shfl_xor(x, 16, 64);
-  if constexpr (NP == 64) x += __shfl_xor(x, 32, 64);
-  return x;
-}
-template <int NP>
-__device__ __forceinline__ double group_max(double x) {
-  x = fmax(x, row_ror<8>(x));
-  x = fmax(x, row_ror<4>(x));
-  x = fmax(x, row_ror<2>(x));
-  x = fmax(x, row_ror<1>(x));
-  if constexpr (NP >= 32) x = fmax(x, __shfl_xor(x, 16, 64));
-  if constexpr (NP == 64) x = fmax(x, __shfl_xor(x, 32, 64));
-  return x;
-}
 
 // sum_k v[lane k of the group] c_k for this lane: c = this lane's 16 coefficients
 // in registers (NP = 16), or column `y` of the LDS image Al [k][NP] above that,
@@ -142,7 +109,7 @@ __device__ __forceinline__ double fwd_step(double al, double e, double sall, con
 }
 
 template <int NP, int NC>
-__global__ __launch_bounds__(kStrWaves * 64) void chain_stream_kernel(StreamArgs a) {
+__global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_kernel(StreamArgs a) {
   constexpr int G = 64 / NP;
   constexpr int NCA = NC > 0 ? NC : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -150,20 +117,12 @@ __global__ __launch_bounds__(kStrWaves * 64) void chain_stream_kernel(StreamArgs
   // then the waves' codes [G][lag + kStreamChunk][NC] (int)
   double* tabs = reinterpret_cast<double*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int row0[NCA], rows = 0;
-#pragma unroll
-  for (int k = 0; k < NC; k++) {
-    row0[k] = rows;
-    const int n = (a.M[k] + 2) * NP;
-    for (int i = tid; i < n; i += kStrWaves * 64) tabs[rows * NP + i] = a.tab[k][(i / NP) * 64 + (i % NP)];
-    rows += a.M[k] + 2;
-  }
-  double* eb = tabs + rows * NP;
-  if (tid < NP) eb[tid] = a.ebase[tid];
+  int row0[NCA];
+  double* eb = stage_tables<NP, NC>(a, tabs, tid, row0);
   double* Af = eb + NP;                                    // Af[x][y] = A[x][y]
   double* Ab = Af + (NP > 16 ? NP * NP : 0);               // Ab[y][x] = A[x][y]
   if constexpr (NP > 16) {
-    for (int i = tid; i < NP * NP; i += kStrWaves * 64) {
+    for (int i = tid; i < NP * NP; i += kGroupWaves * 64) {
       const double v = a.A[(i / NP) * 64 + (i % NP)];
       Af[i] = v;
       Ab[(i % NP) * NP + (i / NP)] = v;
@@ -172,11 +131,11 @@ __global__ __launch_bounds__(kStrWaves * 64) void chain_stream_kernel(StreamArgs
   double* xch0 = Ab + (NP > 16 ? NP * NP : 0);
   double* xch = xch0 + wave * 64;
   const int Wmax = a.lag + kStreamChunk;
-  int* codes = reinterpret_cast<int*>(xch0 + kStrWaves * 64) + wave * (G * Wmax * NC);
+  int* codes = reinterpret_cast<int*>(xch0 + kGroupWaves * 64) + wave * (G * Wmax * NC);
   __syncthreads();
 
   const int grp = lane / NP, y = lane % NP, gbase = grp * NP;
-  const long gw = (long)blockIdx.x * kStrWaves + wave;     // the wave's sequences: gw G .. gw G + G - 1
+  const long gw = (long)blockIdx.x * kGroupWaves + wave;   // the wave's sequences: gw G .. gw G + G - 1
   if (gw * G >= a.B) return;
   const long b = gw * G + grp;
   const bool live = b < a.B;
@@ -198,7 +157,7 @@ __global__ __launch_bounds__(kStrWaves * 64) void chain_stream_kernel(StreamArgs
       int raw;
       if (w < P) raw = a.ring[(bb * L + (s0 + w) % L) * NC + k];
       else raw = a.obs[bb * a.obs_bstride + (long)(w - P) * a.obs_tstride + col];
-      codes[i] = r0 + (raw < 0 ? M : (raw < M ? raw : M + 1));
+      codes[i] = r0 + code_of(raw, M);
     }
     wave_lds_sync();
   }
@@ -332,55 +291,22 @@ __global__ void chain_stream_init_kernel(StreamArgs a, const double* pi64, int N
   }
 }
 
-template <int NP, int NC>
-int str_run(const StreamArgs& a, size_t lds, bool launch, hipStream_t stream) {
-  static size_t lds_set[kMaxDevices] = {};
-  if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_stream_kernel<NP, NC>), lds, lds_set))
-    return rc;
-  if (!launch) return 0;
-  const long waves = (a.B + 64 / NP - 1) / (64 / NP);
-  const dim3 grid((unsigned)((waves + kStrWaves - 1) / kStrWaves)), block(kStrWaves * 64);
-  hipLaunchKernelGGL((chain_stream_kernel<NP, NC>), grid, block, lds, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-template <int NP>
-int str_run_np(const StreamArgs& a, size_t lds, bool launch, hipStream_t stream) {
-  switch (a.ncol) {
-    case 0: return str_run<NP, 0>(a, lds, launch, stream);
-    case 1: return str_run<NP, 1>(a, lds, launch, stream);
-    case 2: return str_run<NP, 2>(a, lds, launch, stream);
-    case 3: return str_run<NP, 3>(a, lds, launch, stream);
-    default: return str_run<NP, 4>(a, lds, launch, stream);
-  }
-}
-
-bool str_shape_ok(const StreamArgs& a) {
-  if (a.N < 1 || a.N > 64 || a.ncol < 0 || a.ncol > 4 || a.nq < 0 || a.nq > kViterbiMaxQuery || a.B < 1 ||
-      a.B > 0x7fffffffL || a.lag < 0 || a.lag > kStreamMaxLag)
-    return false;
-  for (int k = 0; k < a.ncol; k++) if (a.M[k] < 1) return false;
-  for (int j = 0; j < a.nq; j++) if (a.qstride[j] < 1 || a.qcard[j] < 1) return false;
-  return true;
-}
+bool str_shape_ok(const StreamArgs& a) { return cols_shape_ok(a) && a.lag >= 0 && a.lag <= kStreamMaxLag; }
 
 int str_dispatch(const StreamArgs& a, bool launch, hipStream_t stream) {
-  const size_t lds = (chain_stream_lds_bytes(a) + 15) & ~(size_t)15;
-  if (a.N <= 16) return str_run_np<16>(a, lds, launch, stream);
-  if (a.N <= 32) return str_run_np<32>(a, lds, launch, stream);
-  return str_run_np<64>(a, lds, launch, stream);
+  return group_launch(a, chain_stream_lds_bytes(a), launch, stream, [](auto np, auto nc) {
+    return &chain_stream_kernel<decltype(np)::value, decltype(nc)::value>;
+  });
 }
 
 }  // namespace
 
-int chain_stream_np(int N) { return str_np(N); }
+int chain_stream_np(int N) { return group_np(N); }
 
 size_t chain_stream_lds_bytes(const StreamArgs& a) {
-  const int NP = str_np(a.N), G = 64 / NP;
-  size_t rows = 1;                                         // ebase
-  for (int k = 0; k < a.ncol; k++) rows += (size_t)a.M[k] + 2;
-  const size_t dbl = rows * NP + (NP > 16 ? 2 * (size_t)NP * NP : 0) + kStrWaves * 64;
-  const size_t ints = (size_t)kStrWaves * G * (a.lag + kStreamChunk) * a.ncol;
+  const int NP = group_np(a.N), G = 64 / NP;
+  const size_t dbl = evid_rows(a) * NP + (NP > 16 ? 2 * (size_t)NP * NP : 0) + kGroupWaves * 64;
+  const size_t ints = (size_t)kGroupWaves * G * (a.lag + kStreamChunk) * a.ncol;
   return dbl * sizeof(double) + ints * sizeof(int);
 }
 
@@ -398,7 +324,7 @@ int chain_stream_launch(const StreamArgs& a, hipStream_t stream) {
 }
 
 int chain_stream_init_launch(const StreamArgs& a, const double* pi64, hipStream_t stream) {
-  const int NP = str_np(a.N);
+  const int NP = group_np(a.N);
   const long n = a.B * NP;
   hipLaunchKernelGGL(chain_stream_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a, pi64, NP);
   return hipGetLastError() == hipSuccess ? 0 : -1;

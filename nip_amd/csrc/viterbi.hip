@@ -19,10 +19,10 @@
 // exponents are summed into logp.  A power of two changes no comparison, so
 // ties (the lowest index wins) do not depend on the scaling or the lane layout.
 //
-// Layout: NP = 16, 32 or 64 padded states, one NP-lane group per sequence, lane
-// y = state y, 64 / NP sequences per wave, four independent waves per block.
-// Column y of A stays in registers.  delta_{t-1}[x] reaches every lane of its
-// group through a 64-bit DPP row_newbcast operand at NP = 16 (dpp_row.h's
+// Layout: chain_group.h's lane groups (NP = 16, 32 or 64 padded states, one
+// NP-lane group per sequence).  Column y of A stays in registers.
+// delta_{t-1}[x] reaches every lane of its group through a 64-bit DPP
+// row_newbcast operand at NP = 16 (dpp_row.h's
 // v_fmac_f64_dpp onto a zero accumulator: fma(a, b, 0) is the rounded product)
 // and through the wave's own LDS row above that.  The evidence tables are
 // staged in LDS.  The raw observations of step t + 2 are loaded during step t
@@ -45,14 +45,11 @@
 
 #include <cfloat>
 
-#include "chain_kernels.h"
-#include "dpp_row.h"
+#include "chain_group.h"
 
 namespace nipamd {
 
 namespace {
-
-constexpr int kVitWaves = 4;
 
 __host__ __device__ constexpr int vit_log(int NP) { return NP == 16 ? 4 : NP == 32 ? 5 : 6; }
 // words of one wave: T steps of log2(NP) planes, padded to whole 128-byte lines
@@ -77,15 +74,6 @@ __device__ __forceinline__ void fmac_bcast8(double (&p)[16], double v, const dou
       : "v"(v), "v"(c[K0]), "v"(c[K0 + 1]), "v"(c[K0 + 2]), "v"(c[K0 + 3]), "v"(c[K0 + 4]), "v"(c[K0 + 5]),
         "v"(c[K0 + 6]), "v"(c[K0 + 7]), "n"(K0), "n"(K0 + 1), "n"(K0 + 2), "n"(K0 + 3), "n"(K0 + 4),
         "n"(K0 + 5), "n"(K0 + 6), "n"(K0 + 7));
-}
-
-// the maximum over the 16 lanes of the row, in every lane
-__device__ __forceinline__ double row_max(double x) {
-  x = fmax(x, row_ror<8>(x));
-  x = fmax(x, row_ror<4>(x));
-  x = fmax(x, row_ror<2>(x));
-  x = fmax(x, row_ror<1>(x));
-  return x;
 }
 
 // max and lowest argmax of p[0..NP): four chains over ascending quarters,
@@ -128,11 +116,8 @@ __device__ __forceinline__ void vit_step(double d, const double (&Ac)[NP], doubl
     fmac_bcast8<8>(p, d, Ac);
     m = row_max(d);
   } else {
-    // LDS operations of one wave complete in issue order: the wave's own row
-    // needs no barrier, only the compiler kept from reordering the accesses
     xch[lane] = d;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     m = 0.0;
 #pragma unroll
     for (int x = 0; x < NP; x++) {
@@ -140,8 +125,7 @@ __device__ __forceinline__ void vit_step(double d, const double (&Ac)[NP], doubl
       m = fmax(m, dx);
       p[x] = dx * Ac[x];
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
   }
   argmax_low<NP>(p, best, arg);
 }
@@ -155,19 +139,23 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long w, i
 // NC = the observed columns (a.ncol): a constant, so that the observation loads
 // are unconditional and stay in flight over a whole step
 template <int NP, int NC>
-__global__ __launch_bounds__(kVitWaves * 64) void chain_viterbi_kernel(ViterbiArgs a) {
+__global__ __launch_bounds__(kGroupWaves * 64) void chain_viterbi_kernel(ViterbiArgs a) {
   constexpr int LOG = vit_log(NP), SPF = 64 / LOG, RUN = SPF * LOG, G = 64 / NP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* tabs = reinterpret_cast<double*>(smem);        // [rows][NP], ebase [NP], then [waves][64] (NP > 16)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = a.T;
   constexpr int NCA = NC > 0 ? NC : 1;
+  // chain_group.h's stage_tables, written out: through the helper the compiler
+  // schedules this kernel's step loops differently at every NP (it leaves
+  // chain_stream_kernel's code as it is), and mlss measured up to 3.8 % slower
+  // (64 states)
   int row0[NCA], rows = 0;
 #pragma unroll
   for (int k = 0; k < NC; k++) {
     row0[k] = rows;
     const int n = (a.M[k] + 2) * NP;
-    for (int i = tid; i < n; i += kVitWaves * 64) tabs[rows * NP + i] = a.tab[k][(i / NP) * 64 + (i % NP)];
+    for (int i = tid; i < n; i += kGroupWaves * 64) tabs[rows * NP + i] = a.tab[k][(i / NP) * 64 + (i % NP)];
     rows += a.M[k] + 2;
   }
   double* eb = tabs + rows * NP;
@@ -176,7 +164,7 @@ __global__ __launch_bounds__(kVitWaves * 64) void chain_viterbi_kernel(ViterbiAr
   __syncthreads();
 
   const int grp = lane / NP, y = lane % NP, gbase = grp * NP;
-  const long gw = (long)blockIdx.x * kVitWaves + wave;   // the wave's sequences: gw G .. gw G + G - 1
+  const long gw = (long)blockIdx.x * kGroupWaves + wave; // the wave's sequences: gw G .. gw G + G - 1
   if (gw * G >= a.B) return;
   const long b = gw * G + grp;
   const bool live = b < a.B;
@@ -197,10 +185,7 @@ __global__ __launch_bounds__(kVitWaves * 64) void chain_viterbi_kernel(ViterbiAr
   auto evid = [&](const int (&o)[NCA]) {
     double e = eb[y];
 #pragma unroll
-    for (int k = 0; k < NC; k++) {
-      const int M = a.M[k];
-      e *= tabs[(row0[k] + (o[k] < 0 ? M : (o[k] < M ? o[k] : M + 1))) * NP + y];
-    }
+    for (int k = 0; k < NC; k++) e *= tabs[(row0[k] + code_of(o[k], a.M[k])) * NP + y];
     return e;
   };
 
@@ -246,8 +231,7 @@ __global__ __launch_bounds__(kVitWaves * 64) void chain_viterbi_kernel(ViterbiAr
     m = row_max(d);
   } else {
     xch[lane] = d;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     m = 0.0;
 #pragma unroll
     for (int x = 0; x < NP; x++) m = fmax(m, xch[gbase + x]);
@@ -292,55 +276,24 @@ __global__ __launch_bounds__(kVitWaves * 64) void chain_viterbi_kernel(ViterbiAr
   }
 }
 
-template <int NP, int NC>
-int vit_launch_nc(const ViterbiArgs& a, size_t lds, hipStream_t stream) {
-  static size_t lds_set[kMaxDevices] = {};
-  if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_viterbi_kernel<NP, NC>), lds, lds_set))
-    return rc;
-  const long waves = (a.B + 64 / NP - 1) / (64 / NP);
-  const dim3 grid((unsigned)((waves + kVitWaves - 1) / kVitWaves)), block(kVitWaves * 64);
-  hipLaunchKernelGGL((chain_viterbi_kernel<NP, NC>), grid, block, lds, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-template <int NP>
-int vit_launch(const ViterbiArgs& a, size_t lds, hipStream_t stream) {
-  switch (a.ncol) {
-    case 0: return vit_launch_nc<NP, 0>(a, lds, stream);
-    case 1: return vit_launch_nc<NP, 1>(a, lds, stream);
-    case 2: return vit_launch_nc<NP, 2>(a, lds, stream);
-    case 3: return vit_launch_nc<NP, 3>(a, lds, stream);
-    default: return vit_launch_nc<NP, 4>(a, lds, stream);
-  }
-}
-
-int vit_np(int N) { return N <= 16 ? 16 : N <= 32 ? 32 : 64; }
-
 }  // namespace
 
 size_t chain_viterbi_scratch_bytes(int N, long B, int T) {
-  const int NP = vit_np(N), G = 64 / NP;
+  const int NP = group_np(N), G = 64 / NP;
   return (size_t)((B + G - 1) / G) * vit_wave_words(NP, T) * sizeof(unsigned long long);
 }
 
 size_t chain_viterbi_lds_bytes(const ViterbiArgs& a) {
-  const int NP = vit_np(a.N);
-  size_t rows = 1;                                         // ebase
-  for (int k = 0; k < a.ncol; k++) rows += (size_t)a.M[k] + 2;
-  return (rows * NP + (NP > 16 ? kVitWaves * 64 : 0)) * sizeof(double);
+  const int NP = group_np(a.N);
+  return (evid_rows(a) * NP + (NP > 16 ? kGroupWaves * 64 : 0)) * sizeof(double);
 }
 
 int chain_viterbi_launch(const ViterbiArgs& a, hipStream_t stream) {
-  if (a.N < 1 || a.N > 64 || a.ncol < 0 || a.ncol > 4 || a.nq < 1 || a.nq > kViterbiMaxQuery || a.B < 1 ||
-      a.B > 0x7fffffffL || a.T < 1)
-    return kLaunchRefused;
-  for (int k = 0; k < a.ncol; k++) if (a.M[k] < 1) return kLaunchRefused;
-  for (int j = 0; j < a.nq; j++) if (a.qstride[j] < 1 || a.qcard[j] < 1) return kLaunchRefused;
-  const size_t lds = (chain_viterbi_lds_bytes(a) + 15) & ~(size_t)15;
+  if (!cols_shape_ok(a) || a.nq < 1 || a.T < 1) return kLaunchRefused;
   g_last_kernel = "chain_viterbi_kernel";
-  if (a.N <= 16) return vit_launch<16>(a, lds, stream);
-  if (a.N <= 32) return vit_launch<32>(a, lds, stream);
-  return vit_launch<64>(a, lds, stream);
+  return group_launch(a, chain_viterbi_lds_bytes(a), true, stream, [](auto np, auto nc) {
+    return &chain_viterbi_kernel<decltype(np)::value, decltype(nc)::value>;
+  });
 }
 
 }  // namespace nipamd
