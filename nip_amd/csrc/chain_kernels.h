@@ -142,7 +142,9 @@ struct WideArgs : EvidenceArgs {
 };
 __host__ __device__ inline long chain_scratch_row64(int T) { return (long)(T + 2 * kScratchGuard) * 64; }
 size_t chain_wide_lds_bytes(int ncol, int T);
-int chain_wide_launch(const WideArgs& a, hipStream_t stream);
+// every_step: chain_wide_kernel (messages rescaled and ll mantissas renormalised at
+// every step) at 33..64 states too, where chain_row64_kernel runs otherwise
+int chain_wide_launch(const WideArgs& a, hipStream_t stream, bool every_step = false);
 // 33..64 states, four filter waves per direction (chain_wide4.hip); -2: LDS does not fit
 size_t chain_wide4_lds_bytes(const WideArgs& a);
 int chain_wide4_launch(const WideArgs& a, hipStream_t stream);
@@ -414,7 +416,7 @@ int estep_mw_launch(const EMwArgs& a, hipStream_t stream);
 // checkpoint + recompute e_step at 17..32 states (estep_ckw.hip, round 6):
 // one or two observed columns, the same wide slab row per 16 sequences;
 // count_rows = sum over the observed columns of M_k + 2.  Needs the host's
-// underflow bound for rescaling every 4th step (engine_route.cpp ckw_sparse_ok);
+// underflow bound for rescaling every 4th step (engine_route.cpp step_shrink_ok);
 // proper: ll from the final forward mass.  kLaunchRefused when it does not fit.
 size_t chain_estep_ckw_lds_bytes(int tab_rows, int count_rows);
 size_t chain_estep_ckw_scratch_bytes(long B, int T);

@@ -542,8 +542,11 @@ template <bool FWD, int KC, int NE, int PRM>
 __device__ __forceinline__ void estep16_rows(const ChainArgs& a, const double* Et, const uint8_t* codes,
                                              double* Htab, double* m1x, double* kdl, double* p0l, int lane, int grp,
                                              long b0, int nseqb) {
-  constexpr bool PR = PRM != 0;                     // proper mode
-  constexpr bool SP = PRM == 2;                     // and the forward rows may rescale every 4th step
+  constexpr bool PR = (PRM & 3) != 0;               // proper mode
+  constexpr bool SP = (PRM & 3) == 2;               // and the forward rows may rescale every 4th step
+  // PRM & 4: the request is below the step-shrink bound (engine_route.cpp):
+  // the backward rows rescale, and the ll mantissas renormalise, at every step
+  constexpr bool DB = (PRM & 4) != 0;
   const int y = lane & 15, row = lane >> 4;
   const int seq = grp * 4 + row;                    // within the block
   const long b = b0 + seq;
@@ -657,7 +660,8 @@ __device__ __forceinline__ void estep16_rows(const ChainArgs& a, const double* E
     // the forward rows need every step's mass (m2); the backward rows only
     // rescale, every 4th step (j is the unrolled step index: no branch) --
     // four evidence factors cannot underflow, and the exponents carry any scale
-    const bool rescale = (FWD && !PR) || (j & 3) == 3;
+    // (above the step-shrink bound; every step below it, DB)
+    const bool rescale = (FWD && !PR) || (!FWD && DB) || (j & 3) == 3;
     // (the backward rows' rescale needs no sum: the row's largest binary
     // exponent, four integer DPP maxes, serves as well -- NIPAMD_E16_BWD_MAXEXP)
     constexpr bool bmx = !FWD && NIPAMD_E16_BWD_MAXEXP;
@@ -695,7 +699,7 @@ __device__ __forceinline__ void estep16_rows(const ChainArgs& a, const double* E
       m2 *= z2;
       if (combine) m1 *= row_sum(u * s_y);
     }
-    if (!PR && (FWD || combine) && (j & 3) == 3) {  // renormalise every 4 steps (0 stays 0)
+    if (!PR && (FWD || combine) && (DB || (j & 3) == 3)) {  // renormalise every 4 steps (0 stays 0)
       if (FWD) { const int k2 = __builtin_amdgcn_frexp_exp(m2); m2 = __builtin_ldexp(m2, -k2); e2 += k2; }
       const int k1 = __builtin_amdgcn_frexp_exp(m1); m1 = __builtin_ldexp(m1, -k1); e1 += k1;
     }
@@ -949,8 +953,12 @@ static int estep16_launch_pr(const ChainArgs& a, size_t lds, hipStream_t stream)
 }
 template <int NSEQ, int KC, int NE>
 static int estep16_launch(const ChainArgs& a, size_t lds, hipStream_t stream) {
+  // ChainArgs::proper: 0 general, 1 proper, 2 proper with sparse forward
+  // rescaling; + 4 (on 0 or 1): below the step-shrink bound, dense backward rows
   return a.proper == 2 ? estep16_launch_pr<NSEQ, KC, NE, 2>(a, lds, stream)
-       : a.proper      ? estep16_launch_pr<NSEQ, KC, NE, 1>(a, lds, stream)
+       : a.proper == 1 ? estep16_launch_pr<NSEQ, KC, NE, 1>(a, lds, stream)
+       : a.proper == 5 ? estep16_launch_pr<NSEQ, KC, NE, 5>(a, lds, stream)
+       : a.proper == 4 ? estep16_launch_pr<NSEQ, KC, NE, 4>(a, lds, stream)
                         : estep16_launch_pr<NSEQ, KC, NE, 0>(a, lds, stream);
 }
 

@@ -478,14 +478,15 @@ struct WLL {
       const int k1 = __builtin_amdgcn_frexp_exp(m1[q]); m1[q] = __builtin_ldexp(m1[q], -k1); e1[q] += k1;
     }
   }
-  __device__ __forceinline__ void step(int q, double y, double z2, bool last, bool renorm) {
+  // (the mantissas renormalised at every step: the kernel serves the requests
+  // below the step-shrink bound, engine_route.cpp, where a product of four
+  // steps' masses leaves fp64)
+  __device__ __forceinline__ void step(int q, double y, double z2, bool last) {
     zmin[q] = __builtin_fmin(zmin[q], z2);
     m2[q] *= z2;
     if (!last) { m1[q] *= y; e1[q] -= __builtin_amdgcn_frexp_exp(z2); }
-    if (renorm) {
-      const int k2 = __builtin_amdgcn_frexp_exp(m2[q]); m2[q] = __builtin_ldexp(m2[q], -k2); e2[q] += k2;
-      const int k1 = __builtin_amdgcn_frexp_exp(m1[q]); m1[q] = __builtin_ldexp(m1[q], -k1); e1[q] += k1;
-    }
+    const int k2 = __builtin_amdgcn_frexp_exp(m2[q]); m2[q] = __builtin_ldexp(m2[q], -k2); e2[q] += k2;
+    const int k1 = __builtin_amdgcn_frexp_exp(m1[q]); m1[q] = __builtin_ldexp(m1[q], -k1); e1[q] += k1;
   }
   __device__ __forceinline__ void write(const WideMfmaArgs& a, long b0, int lane) {
     if (lane % G::LPC != 0) return;
@@ -542,7 +543,6 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
   auto ll_chunk = [&](int ci, int n, int t0) {
     const double* slot = fring + (ci & 1) * G::kSlot;
     const double* zs = zr + (ci & 1) * CH * kWSeq;
-    const bool full = ci * CH + CH <= n;
     double y[CH * QN];
 #pragma unroll
     for (int k = 0; k < CH; k++)
@@ -559,7 +559,7 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
       const bool last = t0 + i == T - 1;
 #pragma unroll
       for (int q = 0; q < QN; q++)
-        ll.step(q, y[k * QN + q], zs[k * kWSeq + q * CH + hi], last, !full || (k & 3) == 3);
+        ll.step(q, y[k * QN + q], zs[k * kWSeq + q * CH + hi], last);
     }
   };
   double* const sink = FILT ? a.S + 2 * s

@@ -89,7 +89,7 @@ struct WideChain {
 
   template <bool COMBINE>
   __device__ __forceinline__ void step(const WideArgs& a, double* xb, int y, double e, double s,
-                                       double other, double* Sst, double* Pst, bool renorm) {
+                                       double other, double* Sst, double* Pst) {
     const double u = __builtin_ldexp(matvec(xb, y), sc);
     const double p = u * e;
     const double keep = FWD ? p : u;
@@ -97,11 +97,12 @@ struct WideChain {
     if (FWD) {
       const double z1 = wave_sum(u * s);
       zmin = __builtin_fmin(zmin, z2);
+      // the mantissas renormalised at every step: this kernel serves the
+      // requests below the step-shrink bound (engine_route.cpp), where a
+      // product of four steps' masses leaves fp64
       m2 *= z2; m1 *= z1;
-      if (renorm) {
-        const int k2 = __builtin_amdgcn_frexp_exp(m2); m2 = __builtin_ldexp(m2, -k2); e2 += k2;
-        const int k1 = __builtin_amdgcn_frexp_exp(m1); m1 = __builtin_ldexp(m1, -k1); e1 += k1;
-      }
+      const int k2 = __builtin_amdgcn_frexp_exp(m2); m2 = __builtin_ldexp(m2, -k2); e2 += k2;
+      const int k1 = __builtin_amdgcn_frexp_exp(m1); m1 = __builtin_ldexp(m1, -k1); e1 += k1;
     }
     if (!COMBINE) {
       *Sst = keep;
@@ -159,7 +160,7 @@ __device__ void wide_wave(const WideArgs& a, const uint8_t* codes, int Tr, doubl
         if (base + k >= n) break;
         const int t = t0 + dir * (base + k);
         ch.template step<COMBINE>(a, xb, y, e[k], s, o[k], Srow + (long)t * 64,
-                                  Prow ? Prow + (long)t * a.post_tstride : nullptr, (k & 3) == 3);
+                                  Prow ? Prow + (long)t * a.post_tstride : nullptr);
       }
     }
   };
@@ -210,14 +211,14 @@ size_t chain_wide_lds_bytes(int ncol, int T) {
   return 2 * 64 * sizeof(double) + (size_t)(ncol > 0 ? ncol : 1) * chain_codes_row(T);
 }
 
-int chain_wide_launch(const WideArgs& a, hipStream_t stream) {
+int chain_wide_launch(const WideArgs& a, hipStream_t stream, bool every_step) {
   // 33..64 states: the four-waves-per-direction kernel (chain_wide4.hip);
   // NIPAMD_WIDE_KERNEL=wave1 keeps this one-wave form for A/B measurements
   static const bool wave1 = [] {
     const char* e = diag_env("NIPAMD_WIDE_KERNEL");
     return e && std::string(e) == "wave1";
   }();
-  if (a.N > 32 && !wave1) {
+  if (a.N > 32 && !wave1 && !every_step) {
     const int rc = chain_wide4_launch(a, stream);
     if (rc != -2) return rc;
   }

@@ -149,6 +149,7 @@ int ensure_req_tables(nipamd_model* mm, const Route& r, ReqTables** out) {
   for (auto& t : d->reqs) if (t.key == key) { *out = &t; return 0; }
   ReqTables t;
   t.key = key;
+  t.shrink = step_shrink(P, r);
   Staged sg;                                 // every table of the request, one upload
   const int N = P.N;
   if (N <= 16) {

@@ -190,13 +190,13 @@ int estep_mw_partial(nipamd_model* mm, const Route& r, const int32_t* d_obs, int
   const int R = estep_rows(P);
   const int S = nipamd::estep_wide_slab(P.N, R);
   // chain_estep_ckw_kernel (checkpoints + recomputation, round 6): the
-  // default where every step may rescale every 4th step (ckw_sparse_ok) and
+  // default where every step may rescale every 4th step (step_shrink_ok) and
   // its LDS fits; NIPAMD_ESTEP_WIDE_KERNEL=mw in diagnostics builds runs
   // chain_estep_mw_kernel instead
   const char* wk = nipamd::diag_env("NIPAMD_ESTEP_WIDE_KERNEL");
   const bool ck = !(wk && std::string(wk) == "mw") && r.ncol >= 1 && r.ncol <= 2 &&
                   nipamd::chain_estep_ckw_lds_bytes(rt->mtab_rows, rows + 2 * r.ncol) <= nipamd::kLdsPerCU &&
-                  ckw_sparse_ok(P, r, seen);
+                  step_shrink_ok(rt->shrink);
   const long chunk = std::min<long>(B, mw_chunk(ck, T));
   const SlabRun run{S, chunk, 16, ck ? nipamd::chain_estep_ckw_scratch_bytes(chunk, T)
                                      : nipamd::estep_mw_scratch_bytes(chunk, T), {0.0, 0.0, 1.0}};
@@ -360,6 +360,8 @@ int estep_chain_partial(nipamd_model* mm, const Route& r, const int32_t* d_obs, 
     a.counts = slab;
     a.proper = ek == kEstepCk ? (chain_proper(P) ? 1 : 0)
                               : ek == kEstep16 && chain_proper(P) ? (estep16_sparse_ok(P, ne) ? 2 : 1) : 0;
+    // below the step-shrink bound chain_estep16_kernel's backward rows rescale at every step too
+    if (ek == kEstep16 && a.proper != 2 && !step_shrink_ok(step_shrink(P, r))) a.proper |= 4;
 #ifdef NIPAMD_DIAGNOSTICS
     StampBuf stamps;                                   // the first launch's
     if (int rc = stamps.attach(phase_times() && b0 == 0, estep_stamp_words(ek, nb), st, &a.diag)) return rc;

@@ -31,7 +31,7 @@ int launch_cur(nipamd_model* mm, const Route& r, ReqTables* rt, int kind, const 
   if (kind == kMfmaWide) {
     // matrix-core interface chain: N <= 32, up to four observed children
     const int NT = P.N <= 16 ? 1 : 2;
-    if (fb_ckw_ok(P, r, filt, dst != nullptr)) {
+    if (fb_ckw_ok(P, r, rt, filt, dst != nullptr)) {
       if (int rc = ensure_scratch(mm, nipamd::chain_estep_ckw_scratch_bytes(B, T))) return rc;
       nipamd::EMwArgs a{};
       set_obs_view(a, d_obs, n_obs, T);
@@ -65,8 +65,9 @@ int launch_cur(nipamd_model* mm, const Route& r, ReqTables* rt, int kind, const 
 #endif
     return 0;
   }
-  if (kind == kWide64) {
+  if (kind == kWide64 || kind == kWide64Step) {
     // wide interface chain: N <= 64, up to four observed children
+    // (kWide64Step: the kernel that rescales at every step, at 33..64 states too)
     if (int rc = ensure_scratch(mm, filt ? 64 * sizeof(double)
                                          : (size_t)(B + 2) * nipamd::chain_scratch_row64(T) * sizeof(double)))
       return rc;
@@ -80,9 +81,9 @@ int launch_cur(nipamd_model* mm, const Route& r, ReqTables* rt, int kind, const 
     w.ll = d_ll; w.status = d_status;
 #ifdef NIPAMD_DIAGNOSTICS
     StampBuf stamps;                                   // chain_wide4: [block][16]
-    if (int rc = stamps.attach(phase_times() && P.N > 32, (size_t)B * 16, st, &w.diag)) return rc;
+    if (int rc = stamps.attach(phase_times() && P.N > 32 && kind == kWide64, (size_t)B * 16, st, &w.diag)) return rc;
 #endif
-    if (int rc = nipamd::chain_wide_launch(w, st)) return launch_fail(rc, "wide chain kernel");
+    if (int rc = nipamd::chain_wide_launch(w, st, kind == kWide64Step)) return launch_fail(rc, "wide chain kernel");
 #ifdef NIPAMD_DIAGNOSTICS
     if (int rc = stamps.report(st, report_wide4, (long)B)) return rc;
 #endif

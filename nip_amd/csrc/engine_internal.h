@@ -57,6 +57,7 @@ struct ReqTables {
   int mtab_off[4] = {0, 0, 0, 0};
   double* wv = nullptr;           // [64] A s_all
   double* u0 = nullptr;           // [64] pi A: the first slice's prediction (mlss, viterbi.hip)
+  double shrink = 0.0;            // step_shrink of the route (host: the kernel choice reads it per request)
   double* arena = nullptr;        // the pool buffer all of the above live in (one upload)
 };
 
@@ -177,7 +178,11 @@ int chain_scope(const nipamd_model* mm, const std::string& what, const char* sub
 bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int* qstride, int* qcard, int* width);
 bool chain_proper(const ChainPlan& P);
 bool estep16_sparse_ok(const ChainPlan& P, int ne);
-bool ckw_sparse_ok(const ChainPlan& P, const Route& r, const bool (&seen)[4]);
+// the step-shrink bound (engine_route.cpp): kernels that rescale every 4th
+// step take requests at or above kStepShrinkSparse
+constexpr double kStepShrinkSparse = 1e-30;
+double step_shrink(const ChainPlan& P, const Route& r);
+bool step_shrink_ok(double shrink);
 bool observed_children(const ChainPlan& P, const Route& r, bool (&seen)[4], int* rows);
 bool estep_general_plan(const ChainPlan& P);
 int estep_rows(const ChainPlan& P);
@@ -189,10 +194,13 @@ bool has_chain_estep(const Model& m);
 // stages the block's observation codes in LDS, so a long sequence may not fit
 // one and falls through to the next (the 64-state kernel last).  kNoChain:
 // no chain kernel fits -- the request goes to the general engine.
-enum ChainKernel { kNoChain = 0, kMfmaWide, kNarrowMfma, kNarrowDpp, kWide64 };
+// kWide64Step: kWide64 for a request below the step-shrink bound -- the
+// one-wave kernel (chain_wide_kernel, which rescales at every step) at 33..64
+// states too, where kWide64 runs chain_row64_kernel.
+enum ChainKernel { kNoChain = 0, kMfmaWide, kNarrowMfma, kNarrowDpp, kWide64, kWide64Step };
 ChainKernel pick_kernel(const nipamd_model* mm, const Route& r, const ReqTables* rt, int T, bool filt);
 // kMfmaWide: chain_fb_ckw_kernel before chain_mfma_wide_kernel, and its LDS variant
-bool fb_ckw_ok(const ChainPlan& P, const Route& r, bool filt, bool has_dst);
+bool fb_ckw_ok(const ChainPlan& P, const Route& r, const ReqTables* rt, bool filt, bool has_dst);
 bool fb_ckw_vl();
 
 // e_step kernel of the 16-state chain route (kEstepNone: none fits)

@@ -161,18 +161,21 @@ bool observed_children(const ChainPlan& P, const Route& r, bool (&seen)[4], int*
   return true;
 }
 
-// chain_estep_ckw_kernel rescales each recursion every 4th step: allowed when
-// no step can shrink a vector's largest entry by more than 1e-30 (the bound of
-// estep16_sparse_ok at several columns).  For every previous state x: the
+// How much one step can shrink a message: for every previous state x, the
 // largest over y of A[x][y] times the smallest evidence any code combination
-// gives y (per column the smallest of its rows, missing included; column 0
-// carries the unobserved children's row sums).
-bool ckw_sparse_ok(const ChainPlan& P, const Route& r, const bool (&seen)[4]) {
-  if (P.N > 64) return false;
+// gives y (per observed column the smallest of its rows, missing included;
+// the unobserved children's row sums); the smallest of these over x.  A vector
+// whose largest entry is m has one of at least m * step_shrink after a step
+// (the bound of estep16_sparse_ok at several columns).  0 beyond 64 states.
+double step_shrink(const ChainPlan& P, const Route& r) {
+  if (P.N > 64) return 0.0;
   std::vector<double> ev(P.N, 1.0);
-  for (int k = 0; k < (int)P.emits.size() && k < 4; k++)
-    if (!seen[k])
+  for (int k = 0; k < (int)P.emits.size(); k++) {
+    bool seen = false;
+    for (int i = 0; i < r.ncol; i++) seen |= r.emit[i] == k;
+    if (!seen)
       for (int y = 0; y < P.N; y++) ev[y] *= P.emits[k].s[y];
+  }
   for (int i = 0; i < r.ncol; i++) {
     const auto& E = P.emit(r.emit[i]);
     for (int y = 0; y < P.N; y++) {
@@ -181,13 +184,26 @@ bool ckw_sparse_ok(const ChainPlan& P, const Route& r, const bool (&seen)[4]) {
       ev[y] *= lo;
     }
   }
+  double shrink = 1.0;
   for (int x = 0; x < P.N; x++) {
     double best = 0.0;
     for (int y = 0; y < P.N; y++) best = std::max(best, P.A64[x * 64 + y] * ev[y]);
-    if (!(best >= 1e-30)) return false;
+    shrink = std::min(shrink, best);
   }
-  return true;
+  return shrink >= 0.0 ? shrink : 0.0;               // (a NaN table entry: no bound)
 }
+
+// The step-shrink bound, the one verdict that routes a request by its tables'
+// values.  Kernels that rescale their messages every 4th step only
+// (chain_fb_ckpt_kernel, chain_fb_mfma_kernel, chain_fb_ckw_kernel,
+// chain_row64_kernel, chain_estep_ckw_kernel; chain_estep_ck_kernel through
+// estep16_sparse_ok) take a request whose step_shrink is at least 1e-30:
+// either direction's vector then keeps its largest entry above 1e-120 between
+// rescales, the products of the two directions' vectors stay far above the
+// subnormals, and so do the four-step products of step masses their ll
+// mantissas hold.  Any other request goes to a kernel that rescales and
+// renormalises at every step, as the reference does.
+bool step_shrink_ok(double shrink) { return shrink >= kStepShrinkSparse; }
 
 // A chain plan the general 16-state chain e_step takes: one interface
 // variable of at most 16 states, 1..3 leaf children, hidden independent
@@ -263,30 +279,34 @@ ChainKernel pick_kernel(const nipamd_model* mm, const Route& r, const ReqTables*
     const char* e = diag_env("NIPAMD_FB_KERNEL");
     return e && std::string(e) == "wide";
   }();
-  if ((!r.narrow || filt) && P.N <= 32 && !force_wide &&
+  // below the step-shrink bound only kernels that rescale at every step:
+  // chain_mfma_wide_kernel for the narrow requests too, chain_wide_kernel at
+  // any width (kWide64Step), and the general engine where neither fits
+  const bool sparse = step_shrink_ok(rt->shrink);
+  if ((!r.narrow || filt || !sparse) && P.N <= 32 && !force_wide &&
       chain_mfma_wide_lds_bytes(P.N <= 16 ? 1 : 2, rt->mtab_rows, r.ncol, T) <= kLdsPerCU)
     return kMfmaWide;
-  if (r.narrow && !filt) {
+  if (r.narrow && !filt && sparse) {
     if (use_mfma() && chain_mfma_lds_bytes(rt->M0, T) <= kLdsPerCU) return kNarrowMfma;
     if (chain_lds_bytes(rt->M0, T, false) <= kLdsDppKernel) return kNarrowDpp;
   }
-  if (chain_wide_lds_bytes(r.ncol, T) <= kLdsWideKernel) return kWide64;
+  if (chain_wide_lds_bytes(r.ncol, T) <= kLdsWideKernel) return sparse ? kWide64 : kWide64Step;
   return kNoChain;
 }
 
 // kMfmaWide: chain_fb_ckw_kernel (round 6) before chain_mfma_wide_kernel --
 // smoothing at 17..32 states with one or two observed columns where every
-// recursion may rescale every 4th step (ckw_sparse_ok): checkpoints +
+// recursion may rescale every 4th step (step_shrink_ok): checkpoints +
 // recomputation, no message round trip.  NIPAMD_FB_WIDE_KERNEL=mw in
 // diagnostics builds keeps chain_mfma_wide_kernel.  The launcher may still
 // refuse (kLaunchRefused): then chain_mfma_wide_kernel serves the request.
-bool fb_ckw_ok(const ChainPlan& P, const Route& r, bool filt, bool has_dst) {
+bool fb_ckw_ok(const ChainPlan& P, const Route& r, const ReqTables* rt, bool filt, bool has_dst) {
   if (P.N <= 16 || filt || !has_dst || r.ncol < 1 || r.ncol > 2) return false;
   bool seen[4];
   int rows = 0;
   if (!observed_children(P, r, seen, &rows)) return false;
   const char* wk = diag_env("NIPAMD_FB_WIDE_KERNEL");
-  return !(wk && std::string(wk) == "mw") && ckw_sparse_ok(P, r, seen);
+  return !(wk && std::string(wk) == "mw") && step_shrink_ok(rt->shrink);
 }
 
 #ifndef NIPAMD_FB_CKW_VL
@@ -334,7 +354,13 @@ bool chain_estep_ok(const nipamd_model* mm, int n_obs, const int* obs_vars, int 
   } else if (r.ncol > 1 || (r.ncol == 1 && r.emit[0] != 0)) {
     return false;                                  // evidence on the child only
   }
-  return chain_estep_kernel(mm, T) != kEstepNone;
+  // below the step-shrink bound: chain_estep16_kernel in its every-step mode
+  // (engine_estep.cpp) or nothing -- the other kernels of this route go four
+  // steps between rescales whatever the tables, and the wide chain e_step or
+  // the general engine serves the request (estep_partial_routes)
+  const EstepKernel ek = chain_estep_kernel(mm, T);
+  if (ek != kEstepNone && ek != kEstep16 && ek != kEstepCk && !step_shrink_ok(step_shrink(P, r))) return false;
+  return ek != kEstepNone;
 }
 
 // the wide chain e_step: evidence on leaf children only

@@ -275,11 +275,11 @@ __global__ __launch_bounds__(kMsgWaves * 64) void chain_msgs_kernel(EWideArgs a)
           const double z2 = group_sum<NP>(p);
           const double z1 = group_sum<NP>(u * sy);
           zmin = __builtin_fmin(zmin, z2);
+          // renormalised at every step: the route serves the e_steps below
+          // the step-shrink bound, where four steps' masses leave fp64
           m2 *= z2; m1 *= z1;
-          if ((k & 3) == 3) {
-            const int k2 = __builtin_amdgcn_frexp_exp(m2); m2 = __builtin_ldexp(m2, -k2); e2 += k2;
-            const int k1 = __builtin_amdgcn_frexp_exp(m1); m1 = __builtin_ldexp(m1, -k1); e1 += k1;
-          }
+          const int k2 = __builtin_amdgcn_frexp_exp(m2); m2 = __builtin_ldexp(m2, -k2); e2 += k2;
+          const int k1 = __builtin_amdgcn_frexp_exp(m1); m1 = __builtin_ldexp(m1, -k1); e1 += k1;
           sc = z2 != 0.0 ? -__builtin_amdgcn_frexp_exp(z2) : 0;
         }
         x = p;

@@ -74,7 +74,7 @@ def _peaked_hmm():
 
 def _demo1(card, peaked=False, hidden_obs=False):
     nodes, pots = synth.demo1_spec(card)
-    if peaked:                       # (A1 | C1) near the identity: ckw_sparse_ok's bound fails
+    if peaked:                       # (A1 | C1) near the identity: step_shrink_ok's bound fails
         name, par, _ = pots[0]
         pots = [(name, par, _near_identity(card, 1e-50))] + list(pots[1:])
     return (nip_amd.Model.from_spec(nodes, pots), ["A1", "B1"] + (["D1"] if hidden_obs else []), ["C1"])

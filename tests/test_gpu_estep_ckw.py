@@ -1,7 +1,7 @@
 """The checkpoint + recompute e_step at 17..32 states (nip_amd/csrc/
 estep_ckw.hip, chain_estep_ckw_kernel): config 3's default e_step (demo1 @ 32
 states, one or two observed leaf children, hidden parents) when the host's
-rescaling bound holds (engine.cpp ckw_sparse_ok).
+rescaling bound holds (engine_route.cpp step_shrink_ok).
 
 Against the CPU oracle (nip.c:1708-2007 restated, pinned to the reference by
 tests/test_oracle.py) on proper and non-proper models, every T mod 4, ragged

@@ -54,7 +54,7 @@ def demo1_mixed(a, c, peaked=False, b=3, d=2, seed=7):
     """The demo1 structure with a small A1 (a states), B1 (b), D1 (d) and a
     c-state interface C0 -> C1.  peaked: B1 emits (nearly) only state C1 mod b,
     1e-40 elsewhere, which fails the host's bound for rescaling every 4th
-    step (ckw_sparse_ok) and keeps the request on chain_mfma_wide_kernel."""
+    step (step_shrink_ok) and keeps the request on chain_mfma_wide_kernel."""
     if peaked:
         e = np.full((c, b), 1e-40)
         e[np.arange(c), np.arange(c) % b] = 1.0
