@@ -375,7 +375,7 @@ __device__ __forceinline__ void ck_partner(const ChainArgs& a, double* out, doub
         v[q] = *reinterpret_cast<const double2*>(slot + ck_off(k, q * 8 + hi, s));
         z[q] = v[q].x + v[q].y;
       }
-      sum8_n(z);
+      mirror_sum_n<8>(z);
 #pragma unroll
       for (int q = 0; q < 2; q++) {
         const int e = -__builtin_amdgcn_frexp_exp(z[q]);

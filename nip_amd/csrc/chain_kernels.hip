@@ -40,13 +40,12 @@
 #include "chain_kernels.h"
 #include "diag.h"
 #include "dpp_row.h"
+#include "mfma_layout.h"
 #include "store_pol.h"
 
 namespace nipamd {
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));   // an f64 MFMA accumulator
 
 #ifndef NIPAMD_ESTEP_SWZ
 #define NIPAMD_ESTEP_SWZ 0          // e_step: off-critical-path sums on ds_swizzle (A/B build)
@@ -503,35 +502,6 @@ __device__ __forceinline__ void run_phase16(const E16Ctx<NE>& c, int n, int t0, 
       if (base + KC + j < n)
         step(t0 + dir * (base + KC + j), pb.e[j], pb.s[j], pb.x[j], pb.c[j], j, j + 1 < KC ? pb.c[j + 1] : pa.c[0]);
   }
-}
-
-// sum_k x[lane k] * c[k] with two accumulators (dot_bcast has four): two
-// zeroing moves and one add per mat-vec instead of four and three; the
-// other wave on the SIMD covers the longer fma chains
-__device__ __forceinline__ double dot2_bcast(double x, const double (&c)[16]) {
-  double a0 = 0.0, a1 = 0.0;
-  fmac_bcast<0, true>(a0, x, c[0]);   fmac_bcast<1, false>(a1, x, c[1]);
-  fmac_bcast<2, false>(a0, x, c[2]);  fmac_bcast<3, false>(a1, x, c[3]);
-  fmac_bcast<4, false>(a0, x, c[4]);  fmac_bcast<5, false>(a1, x, c[5]);
-  fmac_bcast<6, false>(a0, x, c[6]);  fmac_bcast<7, false>(a1, x, c[7]);
-  fmac_bcast<8, false>(a0, x, c[8]);  fmac_bcast<9, false>(a1, x, c[9]);
-  fmac_bcast<10, false>(a0, x, c[10]); fmac_bcast<11, false>(a1, x, c[11]);
-  fmac_bcast<12, false>(a0, x, c[12]); fmac_bcast<13, false>(a1, x, c[13]);
-  fmac_bcast<14, false>(a0, x, c[14]); fmac_bcast<15, false>(a1, x, c[15]);
-  return a0 + a1;
-}
-
-// 16-lane integer max of the lanes' binary exponents (zeros excluded): the
-// rescale exponent of a proper model's forward rows, every step -- four DPP
-// integer ops where the row's f64 sum was twelve (any power of two serves:
-// the ll no longer reads the step masses, posteriors and xi are scale-free)
-__device__ __forceinline__ int row_max_exp_rescale(double p) {
-  int e = p != 0.0 ? __builtin_amdgcn_frexp_exp(p) : -0x40000;
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x128, 0xF, 0xF, true));   // row_ror:8
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x124, 0xF, 0xF, true));   // row_ror:4
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x122, 0xF, 0xF, true));   // row_ror:2
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x121, 0xF, 0xF, true));   // row_ror:1
-  return e > -0x40000 ? -e : 0;
 }
 
 // One direction's rows of a block (FWD: waves 0-3, backward: waves 4-7).

@@ -148,7 +148,7 @@ __device__ __forceinline__ void estep_phase_b(const ChainArgs& a, double* out, c
         double v[16], o[16], e[16];
 #pragma unroll
         for (int p = 0; p < 8; p++) {
-          const double2 x = *reinterpret_cast<const double2*>(vr + piece_off(c, p));
+          const double2 x = *reinterpret_cast<const double2*>(vr + piece_off<16>(c, p));
           v[2 * p] = x.x; v[2 * p + 1] = x.y;
           const double2 w = *reinterpret_cast<const double2*>(orow + 2 * p);
           o[2 * p] = w.x; o[2 * p + 1] = w.y;
@@ -182,7 +182,7 @@ __device__ __forceinline__ void estep_phase_b(const ChainArgs& a, double* out, c
         if (!FWD) {
 #pragma unroll
           for (int p = 0; p < 8; p++)
-            *reinterpret_cast<double2*>(vr + piece_off(c, p)) =
+            *reinterpret_cast<double2*>(vr + piece_off<16>(c, p)) =
                 make_double2(ok ? e[2 * p] * v[2 * p] : 0.0, ok ? e[2 * p + 1] * v[2 * p + 1] : 0.0);
         }
       }
@@ -193,7 +193,7 @@ __device__ __forceinline__ void estep_phase_b(const ChainArgs& a, double* out, c
     // 2. xi on the matrix cores
 #pragma unroll
     for (int cc = 0; cc < kMSeq; cc++) {
-      const int po = piece_off(cc, y >> 1) + (y & 1);
+      const int po = piece_off<16>(cc, y >> 1) + (y & 1);
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         const int k = 4 * h + kq;
@@ -208,7 +208,7 @@ __device__ __forceinline__ void estep_phase_b(const ChainArgs& a, double* out, c
       }
     }
 #pragma unroll
-    for (int cc = 0; cc < kMSeq; cc++) pv[cc] = slot[(kMChunk - 1) * kStepD + piece_off(cc, y >> 1) + (y & 1)];
+    for (int cc = 0; cc < kMSeq; cc++) pv[cc] = slot[(kMChunk - 1) * kStepD + piece_off<16>(cc, y >> 1) + (y & 1)];
     tick(2);
     // 3. posteriors over the xi operands
 #pragma unroll
@@ -265,8 +265,8 @@ __device__ __forceinline__ void estep_phase_b(const ChainArgs& a, double* out, c
     const int m = (lane >> 4) + 4 * r;                   // D row: the observation code
     if (m < M) slab[hoff + m * 16 + y] = hc[r];
   }
-  miss = sum_lanes16(sum_lanes32(miss));                  // the four steps kq of state y
-  if (!FWD) p0 = sum_lanes16(sum_lanes32(p0));
+  miss = xor16_sum(xor32_sum(miss));                  // the four steps kq of state y
+  if (!FWD) p0 = xor16_sum(xor32_sum(p0));
   if (lane < 16) {
     slab[hoff + M * 16 + y] = miss;
     slab[hoff + (M + 1) * 16 + y] = 0.0;
@@ -312,7 +312,7 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
   auto ring_vec = [&](const double* slot, int k, double (&v)[16]) {
 #pragma unroll
     for (int p = 0; p < 8; p++) {
-      const double2 x = *reinterpret_cast<const double2*>(slot + k * kStepD + piece_off(c, p));
+      const double2 x = *reinterpret_cast<const double2*>(slot + k * kStepD + piece_off<16>(c, p));
       v[2 * p] = x.x; v[2 * p + 1] = x.y;
     }
   };
@@ -347,7 +347,7 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
 #pragma unroll
       for (int q = 0; q < 2; q++) {
         const int jj = q * 8 + hi;
-        const double2 v = *reinterpret_cast<const double2*>(slot + k * kStepD + piece_off(jj, s));
+        const double2 v = *reinterpret_cast<const double2*>(slot + k * kStepD + piece_off<16>(jj, s));
         *reinterpret_cast<double2*>(Sblk + (long)t * kSStep + jj * 16 + 2 * s) = v;
       }
     }
@@ -368,7 +368,7 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
     const int yy = lane & 15;
 #pragma unroll
     for (int cc = 0; cc < kMSeq; cc++)
-      pv[cc] = !FWD ? 0.0 : nA > 0 ? src[piece_off(cc, yy >> 1) + (yy & 1)] : a.pi[yy];
+      pv[cc] = !FWD ? 0.0 : nA > 0 ? src[piece_off<16>(cc, yy >> 1) + (yy & 1)] : a.pi[yy];
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // phase barrier
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -417,7 +417,7 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
         const double r = recip((z0 + z1) + (z2 + z3));    // an all-zero row stays zero
 #pragma unroll
         for (int p = 0; p < 8; p++)
-          *reinterpret_cast<double2*>(slot + k * kStepD + piece_off(c, p)) = make_double2(pr[2 * p] * r, pr[2 * p + 1] * r);
+          *reinterpret_cast<double2*>(slot + k * kStepD + piece_off<16>(c, p)) = make_double2(pr[2 * p] * r, pr[2 * p + 1] * r);
       }
       if (FWD) ll.renorm();
     };
@@ -438,7 +438,7 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
 #endif
 #pragma unroll
       for (int q = 0; q < kMSeq; q++) {
-        const double2 v = *reinterpret_cast<const double2*>(slot + kB * kStepD + piece_off(q, s));
+        const double2 v = *reinterpret_cast<const double2*>(slot + kB * kStepD + piece_off<16>(q, s));
 #if NIPAMD_MFMA_ABLATE == 11
         if (v.x == 12345.0)
 #endif
@@ -517,11 +517,11 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
           double px[8], py[8], z[8], r[8];
 #pragma unroll
           for (int i = 0; i < 8; i++) {
-            const double2 v = *reinterpret_cast<const double2*>(slot + kB * kStepD + piece_off(q0 + i, s));
+            const double2 v = *reinterpret_cast<const double2*>(slot + kB * kStepD + piece_off<16>(q0 + i, s));
             px[i] = v.x * o[q0 + i].x; py[i] = v.y * o[q0 + i].y;
             z[i] = px[i] + py[i];
           }
-          sum8_n(z);
+          mirror_sum_n<8>(z);
           recip_n(z, r);                                 // an all-zero row stays zero
 #pragma unroll
           for (int i = 0; i < 8; i++) {
@@ -535,9 +535,9 @@ __device__ __forceinline__ void partner_wave(const ChainArgs& a, double* out, co
       } else {
 #pragma unroll
         for (int q = 0; q < kMSeq; q++) {
-          const double2 v = *reinterpret_cast<const double2*>(slot + kB * kStepD + piece_off(q, s));
+          const double2 v = *reinterpret_cast<const double2*>(slot + kB * kStepD + piece_off<16>(q, s));
           const double px = v.x * o[q].x, py = v.y * o[q].y;
-          const double r = recip(sum8(px + py));
+          const double r = recip(mirror_sum<8>(px + py));
           const long bb = b0 + q;
           if (!ok || bb >= a.B) continue;
           double* p = a.post + (size_t)bb * a.post_bstride + (long)t * a.post_tstride + a.post_off + 2 * s;
@@ -669,8 +669,8 @@ void chain_fb_mfma_kernel(ChainArgs a) {
   c.zr = zr;
   c.scr = ES ? scr_d : nullptr;
   c.zw = g == 0;
-  c.wo0 = piece_off(j, g);
-  c.wo1 = piece_off(j, 4 + g);
+  c.wo0 = piece_off<16>(j, g);
+  c.wo1 = piece_off<16>(j, 4 + g);
   if (fwd) filter_wave<true, ES>(a, c, Et, Sw, lane, active, b, nchA, nchB, stamps);
   else filter_wave<false, ES>(a, c, Et, Sw, lane, active, b, nchA, nchB, nullptr);
   if (ES) diag_stamp(a, fwd ? 3 : 4, lane);

@@ -1,8 +1,10 @@
 // chain_mfma_core.h -- the matrix-core chain pieces shared by the
 // forward-backward kernels of chain_mfma.hip (scratch round trip) and
-// chain_ckpt.hip (checkpoints + recompute): register layout, reductions, the
-// filter step (Chain), the forward partner's log-likelihood (LL).  Included
-// once per translation unit, inside an anonymous namespace.
+// chain_ckpt.hip (checkpoints + recompute): their constants, the mat-vec, the
+// LDS-DMA helpers, the filter step (WaveCtx, Chain), the forward partner's
+// log-likelihood (LL).  The register layout is mfma_layout.h's, the lane sums
+// dpp_row.h's and wave_ops.h's.  Included once per translation unit, inside an
+// anonymous namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -10,12 +12,11 @@
 #include <utility>
 
 #include "chain_kernels.h"
+#include "mfma_layout.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double v2d __attribute__((ext_vector_type(2)));
 
 #ifndef NIPAMD_MFMA_ABLATE
 #define NIPAMD_MFMA_ABLATE 0       // timing-only builds: 11 no posterior stores, 12 no phase-B loads,
@@ -48,70 +49,9 @@ constexpr int kOBRow = 130;                        // DMA buffer doubles per cha
 
 __host__ __device__ inline long block_scratch(int T) { return (long)(T + 2 * kMG) * kSStep; }
 
-__device__ __forceinline__ double sum_lanes32(double x) {   // x[l] + x[l ^ 32]
-  double xc = x;
-  asm("" : "+v"(xc));   // the swap's second operand: a whole-double copy (one v_mov_b64)
-  const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-
-__device__ __forceinline__ double sum_lanes16(double x) {   // x[l] + x[l ^ 16]
-  double xc = x;
-  asm("" : "+v"(xc));   // the swap's second operand: a whole-double copy (one v_mov_b64)
-  const auto rl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-
 // sum of the chain's 16 states, identical in the chain's four lanes
 __device__ __forceinline__ double chain_sum(v4d v) {
-  return sum_lanes16(sum_lanes32((v.x + v.y) + (v.z + v.w)));
-}
-
-// DPP move of a double within a 16-lane row (32-bit halves; full row mask)
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-// sum over aligned groups of 8 lanes (quad swaps, then row_half_mirror);
-// every level pairs equal partial sums, so all 8 lanes get identical bits
-__device__ __forceinline__ double sum8(double x) {
-  asm("" : "+v"(x));       // one rounded value per lane: no fma contraction into the first add
-  x += dpp64<0xB1>(x);     // quad_perm [1,0,3,2]
-  x += dpp64<0x4E>(x);     // quad_perm [2,3,0,1]
-  x += dpp64<0x141>(x);    // row_half_mirror
-  return x;
-}
-
-// sum8 of n independent values, level by level so the n dependency chains
-// interleave (one wave per SIMD: nothing else hides the f64 latency)
-template <int n>
-__device__ __forceinline__ void sum8_n(double (&x)[n]) {
-#pragma unroll
-  for (int i = 0; i < n; i++) asm("" : "+v"(x[i]));   // see sum8
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += dpp64<0xB1>(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += dpp64<0x4E>(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += dpp64<0x141>(x[i]);
-}
-
-// 1/c for n values, staged like sum8_n; 0 where c == 0
-template <int n>
-__device__ __forceinline__ void recip_n(const double (&c)[n], double (&r)[n]) {
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = __builtin_amdgcn_rcp(c[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = __builtin_fma(r[i], __builtin_fma(-c[i], r[i], 1.0), r[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = __builtin_fma(r[i], __builtin_fma(-c[i], r[i], 1.0), r[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = c[i] != 0.0 ? r[i] : 0.0;
+  return xor16_sum(xor32_sum((v.x + v.y) + (v.z + v.w)));
 }
 
 #ifndef NIPAMD_MFMA_SPLITK
@@ -138,47 +78,6 @@ __device__ __forceinline__ v4d matvec(const double (&Aop)[4], v4d X) {
 #endif
 }
 
-__device__ __forceinline__ v4d ldexp4(v4d v, int k) {
-  v4d r;
-  r.x = __builtin_ldexp(v.x, k); r.y = __builtin_ldexp(v.y, k);
-  r.z = __builtin_ldexp(v.z, k); r.w = __builtin_ldexp(v.w, k);
-  return r;
-}
-
-// v with the entries zeroed whose entry of m is 0 (a select, never a product:
-// v may hold inf)
-__device__ __forceinline__ v4d zero_where_zero(v4d v, const v4d& m) {
-  v.x = m.x != 0.0 ? v.x : 0.0; v.y = m.y != 0.0 ? v.y : 0.0;
-  v.z = m.z != 0.0 ? v.z : 0.0; v.w = m.w != 0.0 ? v.w : 0.0;
-  return v;
-}
-
-// 1/c (v_rcp_f64 + two Newton steps); 0 when c == 0 so that an all-zero
-// array stays zero (nip_normalise_array, nippotential.c:354)
-__device__ __forceinline__ double recip(double c) {
-  double r = __builtin_amdgcn_rcp(c);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  return c != 0.0 ? r : 0.0;
-}
-
-// actual state held by register r of lane group g
-__host__ __device__ constexpr int state_of(int g, int r) { return r < 2 ? 2 * g + r : 6 + 2 * g + r; }
-
-// this lane's four states of a 16-state row; p = row + 2g
-__device__ __forceinline__ v4d load4(const double* p) {
-  const double2 a = *reinterpret_cast<const double2*>(p);
-  const double2 b = *reinterpret_cast<const double2*>(p + 8);
-  v4d r;
-  r.x = a.x; r.y = a.y; r.z = b.x; r.w = b.y;
-  return r;
-}
-
-// LDS ring layout of one step: chain j's 16 states at j*16, its eight 16-byte
-// pieces XOR-swizzled by (j & 7) so that the filter's writes and the
-// partner's reads are bank-conflict free.
-__device__ __forceinline__ int piece_off(int j, int s) { return j * 16 + ((s ^ (j & 7)) << 1); }
-
 #ifndef NIPAMD_WAIT_TIMES
 #define NIPAMD_WAIT_TIMES 0        // diagnostics build: per-wave barrier wait cycles into the stamps
 #endif
@@ -186,14 +85,15 @@ struct WaitAcc {
   unsigned long long cyc = 0;
 };
 
-__device__ __forceinline__ void barrier_lds(WaitAcc* w = nullptr) {
+// barrier_lds() with the wait's cycles added to w (diagnostics builds)
+__device__ __forceinline__ void barrier_lds(WaitAcc* w) {
 #if NIPAMD_WAIT_TIMES
   const unsigned long long t0 = __builtin_readcyclecounter();
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  barrier_lds();
   if (w) w->cyc += __builtin_readcyclecounter() - t0;
 #else
   (void)w;
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  barrier_lds();
 #endif
 }
 

@@ -35,14 +35,13 @@
 #include <cstdint>
 
 #include "chain_kernels.h"
+#include "mfma_layout.h"
 #include "store_pol.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double v2d __attribute__((ext_vector_type(2)));
 
 #ifndef NIPAMD_MW_ABLATE
 #define NIPAMD_MW_ABLATE 0     // timing-only builds: 1 partners only keep the barriers,
@@ -57,75 +56,6 @@ constexpr int kWSeq = 16;                  // sequences per group
 constexpr int kWGroups = 2;                // groups per block
 constexpr int kWThreads = 512;
 constexpr int kWG = kScratchGuard;
-
-__host__ __device__ constexpr int state_of(int g, int r) { return r < 2 ? 2 * g + r : 6 + 2 * g + r; }
-
-__device__ __forceinline__ double swap32_sum(double x) {     // x[l] + x[l ^ 32]
-  double xc = x;
-  asm("" : "+v"(xc));   // the swap's second operand: a whole-double copy (one v_mov_b64)
-  const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-
-__device__ __forceinline__ double swap16_sum(double x) {     // x[l] + x[l ^ 16]
-  double xc = x;
-  asm("" : "+v"(xc));   // the swap's second operand: a whole-double copy (one v_mov_b64)
-  const auto rl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-// sums over aligned groups of L = 8 or 16 lanes, level by level over n
-// independent values; every level pairs equal partial sums (or adds a value
-// to its mirror), so all lanes of a group hold identical bits
-template <int L, int n>
-__device__ __forceinline__ void sumL_n(double (&x)[n]) {
-#pragma unroll
-  for (int i = 0; i < n; i++) asm("" : "+v"(x[i]));   // one rounded value per lane: no fma contraction
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += dpp64<0xB1>(x[i]);     // quad_perm [1,0,3,2]
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += dpp64<0x4E>(x[i]);     // quad_perm [2,3,0,1]
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += dpp64<0x141>(x[i]);    // row_half_mirror
-  if (L == 16) {
-#pragma unroll
-    for (int i = 0; i < n; i++) x[i] += dpp64<0x140>(x[i]);  // row_mirror
-  }
-}
-
-template <int n>
-__device__ __forceinline__ void recip_n(const double (&c)[n], double (&r)[n]) {
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = __builtin_amdgcn_rcp(c[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = __builtin_fma(r[i], __builtin_fma(-c[i], r[i], 1.0), r[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = __builtin_fma(r[i], __builtin_fma(-c[i], r[i], 1.0), r[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) r[i] = c[i] != 0.0 ? r[i] : 0.0;   // all-zero rows stay zero
-}
-
-__device__ __forceinline__ v4d ldexp4(v4d v, int k) {
-  v4d r;
-  r.x = __builtin_ldexp(v.x, k); r.y = __builtin_ldexp(v.y, k);
-  r.z = __builtin_ldexp(v.z, k); r.w = __builtin_ldexp(v.w, k);
-  return r;
-}
-
-__device__ __forceinline__ v4d load4(const double* p) {      // p = row + 16q + 2g
-  const v2d a = *reinterpret_cast<const v2d*>(p);
-  const v2d b = *reinterpret_cast<const v2d*>(p + 8);
-  return v4d{a.x, a.y, b.x, b.y};
-}
 
 #ifndef NIPAMD_WAIT_TIMES
 #define NIPAMD_WAIT_TIMES 0        // stamps builds: per-wave phase and barrier-wait cycles (a.diag)
@@ -147,14 +77,15 @@ struct MwDiag {
   }
 };
 
-__device__ __forceinline__ void barrier_lds(MwDiag* dg = nullptr) {
+// barrier_lds() with the wait's cycles added to the current phase's total
+__device__ __forceinline__ void barrier_lds(MwDiag* dg) {
 #if NIPAMD_WAIT_TIMES
   const unsigned long long t = __builtin_readcyclecounter();
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  barrier_lds();
   if (dg) (dg->inB ? dg->wb : dg->wa) += __builtin_readcyclecounter() - t;
 #else
   (void)dg;
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  barrier_lds();
 #endif
 }
 
@@ -170,8 +101,6 @@ struct Geo {
   // all at bank 0 (an NP-double row is 128 or 256 B: 16-way conflicts)
   static constexpr int NPS = NP + 2;
   static constexpr int kSlot = CH * kStep;    // doubles per ring slot (16 KB)
-  // chain j's piece p (16 bytes) within a step, XOR-swizzled by j & 7
-  __device__ static int piece_off(int j, int p) { return j * NP + ((p ^ (j & 7)) << 1); }
 };
 
 __host__ __device__ inline long wblock_scratch(int NT, int T) { return (long)(T + 2 * kWG) * kWSeq * 16 * NT; }
@@ -237,7 +166,7 @@ struct WChain {
 #pragma unroll
     for (int k = 0; k < NC; k++) {
 #pragma unroll
-      for (int q = 0; q < NT; q++) r[k][q] = load4(c.tab + c.tab_off[k] + cd[k] * G::NPS + 16 * q);
+      for (int q = 0; q < NT; q++) r[k][q] = load4v(c.tab + c.tab_off[k] + cd[k] * G::NPS + 16 * q);
     }
   }
   __device__ __forceinline__ void product(const WCtx& c, const v4d (&r)[NC][NT], v4d (&e)[NT]) const {
@@ -308,12 +237,12 @@ struct WChain {
     }
     if (AN && c.zw) Ez[c.j] = E;
     if (!RS) { sc = 0; return; }
-    const double z2 = swap16_sum(swap32_sum(part));
+    const double z2 = xor16_sum(xor32_sum(part));
     const int k = __builtin_amdgcn_frexp_exp(z2);
     if (AN && FWD) {
       // m2_t = z2_t; m1_{t+1} = 2^sc_{t+1} y_t, y_t = alpha^_t . w
       asm("" : "+v"(py));
-      const double y = swap16_sum(swap32_sum(py));
+      const double y = xor16_sum(xor32_sum(py));
       zmin = __builtin_fmin(zmin, z2);
       m2 *= z2;
       if (!last) { m1 *= y; e1 -= k; }
@@ -392,15 +321,15 @@ __device__ __forceinline__ void wfilter(const WideMfmaArgs& a, const WCtx& c, do
     double py = 0.0;
 #pragma unroll
     for (int q = 0; q < NT; q++) {
-      ch.X[q] = load4(a.pi + 16 * q + 2 * g);
+      ch.X[q] = load4v(a.pi + 16 * q + 2 * g);
       if (AN) {
-        ch.wv[q] = load4(a.w + 16 * q + 2 * g);
+        ch.wv[q] = load4v(a.w + 16 * q + 2 * g);
         py += (ch.X[q].x * ch.wv[q].x + ch.X[q].y * ch.wv[q].y) + (ch.X[q].z * ch.wv[q].z + ch.X[q].w * ch.wv[q].w);
       }
     }
     if (AN) {
       asm("" : "+v"(py));
-      ch.m1 = swap16_sum(swap32_sum(py));                 // y_{-1} = prior . w
+      ch.m1 = xor16_sum(xor32_sum(py));                 // y_{-1} = prior . w
       ch.renorm();
     }
   } else {
@@ -419,7 +348,7 @@ __device__ __forceinline__ void wfilter(const WideMfmaArgs& a, const WCtx& c, do
       part += (ch.X[q].x + ch.X[q].y) + (ch.X[q].z + ch.X[q].w);
     }
     if (AN && g == 0) Eblk[(long)(T - 1) * kWSeq + j] = 0;     // its exponent
-    ch.sc = -__builtin_amdgcn_frexp_exp(swap16_sum(swap32_sum(part)));
+    ch.sc = -__builtin_amdgcn_frexp_exp(xor16_sum(xor32_sum(part)));
   }
   MwDiag dg;
   dg.start();
@@ -456,7 +385,7 @@ struct WLL {
   __device__ __forceinline__ void init(const WideMfmaArgs& a, int s, bool first = true) {
     w0 = a.w[2 * s]; w1 = a.w[2 * s + 1];
     double y[1] = {a.pi[2 * s] * w0 + a.pi[2 * s + 1] * w1};
-    sumL_n<G::LPC>(y);
+    mirror_sum_n<G::LPC>(y);
 #pragma unroll
     for (int q = 0; q < G::QN; q++) { m2[q] = 1.0; m1[q] = first ? y[0] : 1.0; zmin[q] = 1.0; e2[q] = 0; e1[q] = 0; }
   }
@@ -548,10 +477,10 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
     for (int k = 0; k < CH; k++)
 #pragma unroll
       for (int q = 0; q < QN; q++) {
-        const v2d v = *reinterpret_cast<const v2d*>(slot + k * G::kStep + G::piece_off(q * CH + hi, s));
+        const v2d v = *reinterpret_cast<const v2d*>(slot + k * G::kStep + piece_off<G::NP>(q * CH + hi, s));
         y[k * QN + q] = v.x * ll.w0 + v.y * ll.w1;
       }
-    sumL_n<LPC>(y);
+    mirror_sum_n<LPC>(y);
 #pragma unroll
     for (int k = 0; k < CH; k++) {
       const int i = ci * CH + k;
@@ -572,11 +501,11 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
       double px[8], py[8], z[8], r[8];
 #pragma unroll
       for (int i = 0; i < 8; i++) {
-        const v2d v = *reinterpret_cast<const v2d*>(slot + kk * G::kStep + G::piece_off(q0 + i, s));
+        const v2d v = *reinterpret_cast<const v2d*>(slot + kk * G::kStep + piece_off<G::NP>(q0 + i, s));
         px[i] = v.x * o[q0 + i].x; py[i] = v.y * o[q0 + i].y;
         z[i] = px[i] + py[i];
       }
-      sumL_n<LPC>(z);
+      mirror_sum_n<LPC>(z);
       recip_n(z, r);
 #pragma unroll
       for (int i = 0; i < 8; i++) {
@@ -617,7 +546,7 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
 #pragma unroll
       for (int u0 = 0; u0 < kWSeq * LPC; u0 += 64) {
         const int u = u0 + lane, jj = u / LPC, p = u % LPC;
-        const v2d v = *reinterpret_cast<const v2d*>(slot + k * G::kStep + G::piece_off(jj, p));
+        const v2d v = *reinterpret_cast<const v2d*>(slot + k * G::kStep + piece_off<G::NP>(jj, p));
         store_pol<NIPAMD_WIDE_SCR_NT>(reinterpret_cast<v2d*>(Sblk + (long)t * G::kStep + 2 * u), v);
       }
       if (AN && lane < kWSeq) Eblk[(long)t * kWSeq + lane] = er[((ci & 1) * CH + k) * kWSeq + lane];
@@ -653,7 +582,7 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
   auto emit_an = [&](const double* slot, const int* es, int kk, int t, bool ok, const v2d (&o)[kWSeq]) {
 #pragma unroll
     for (int q = 0; q < kWSeq; q++) {
-      const v2d v = *reinterpret_cast<const v2d*>(slot + kk * G::kStep + G::piece_off(q, s));
+      const v2d v = *reinterpret_cast<const v2d*>(slot + kk * G::kStep + piece_off<G::NP>(q, s));
       const v2d z = *reinterpret_cast<const v2d*>(cz + 2 * q);
       const double f = __builtin_ldexp(z.x, (int)z.y - es[kk * kWSeq + q] - eo[q]);
       const double px = v.x * o[q].x * f, py = v.y * o[q].y * f;
@@ -687,10 +616,10 @@ __device__ __forceinline__ void wpartner(const WideMfmaArgs& a, const double* ou
           double z[8];
 #pragma unroll
           for (int i = 0; i < 8; i++) {
-            const v2d v = *reinterpret_cast<const v2d*>(slot + kB * G::kStep + G::piece_off(q0 + i, s));
+            const v2d v = *reinterpret_cast<const v2d*>(slot + kB * G::kStep + piece_off<G::NP>(q0 + i, s));
             z[i] = v.x * o[q0 + i].x + v.y * o[q0 + i].y;
           }
-          sumL_n<LPC>(z);
+          mirror_sum_n<LPC>(z);
           double r[8];
           recip_n(z, r);
           if (kB == 0 && s == 0) {
@@ -803,8 +732,8 @@ void chain_mfma_wide_kernel(WideMfmaArgs a) {
   c.j = j;
 #pragma unroll
   for (int q = 0; q < NT; q++) {
-    c.wo[q][0] = Geo<NT>::piece_off(j, 8 * q + g);
-    c.wo[q][1] = Geo<NT>::piece_off(j, 8 * q + 4 + g);
+    c.wo[q][0] = piece_off<Geo<NT>::NP>(j, 8 * q + g);
+    c.wo[q][1] = piece_off<Geo<NT>::NP>(j, 8 * q + 4 + g);
   }
   if (fwd) wfilter<true, NT, NC, AN>(a, c, Sblk, Eblk, lane, b0, nchA, nchB);
   else if (!FILT) wfilter<false, NT, NC, AN>(a, c, Sblk, Eblk, lane, b0, nchA, nchB);

@@ -23,6 +23,7 @@
 
 #include "chain_kernels.h"
 #include "diag.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 
@@ -30,41 +31,6 @@ namespace {
 
 constexpr int kWG = kScratchGuard;
 constexpr int kWChunk = 8;
-
-template <int K>
-__device__ __forceinline__ double ror64(double v) {     // row_ror:K of a double
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x120 + K, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x120 + K, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-  asm("" : "+v"(x));       // one rounded value per lane: no fma contraction into the first add
-  x += ror64<8>(x);
-  x += ror64<4>(x);
-  x += ror64<2>(x);
-  x += ror64<1>(x);
-  {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    x = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-  }
-  {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    x = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-  }
-  return x;
-}
-
-__device__ __forceinline__ double recip(double c) {
-  double r = __builtin_amdgcn_rcp(c);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  return c != 0.0 ? r : 0.0;
-}
 
 template <bool FWD, int NP>
 struct WideChain {
@@ -93,9 +59,9 @@ struct WideChain {
     const double u = __builtin_ldexp(matvec(xb, y), sc);
     const double p = u * e;
     const double keep = FWD ? p : u;
-    const double z2 = wave_sum(p);
+    const double z2 = lanes_sum<64>(p);
     if (FWD) {
-      const double z1 = wave_sum(u * s);
+      const double z1 = lanes_sum<64>(u * s);
       zmin = __builtin_fmin(zmin, z2);
       // the mantissas renormalised at every step: this kernel serves the
       // requests below the step-shrink bound (engine_route.cpp), where a
@@ -108,7 +74,7 @@ struct WideChain {
       *Sst = keep;
     } else {
       const double pr = keep * other;
-      const double q = pr * recip(wave_sum(pr));
+      const double q = pr * recip(lanes_sum<64>(pr));
       if (Pst) *Pst = q;
     }
     sc = -__builtin_amdgcn_frexp_exp(z2);
@@ -141,7 +107,7 @@ __device__ void wide_wave(const WideArgs& a, const uint8_t* codes, int Tr, doubl
     const double beta = y < a.N ? 1.0 : 0.0;
     Srow[(long)(T - 1) * 64] = beta;                  // beta_{T-1}, T-1 >= H
     ch.X = evidence(T - 1) * beta;
-    ch.sc = -__builtin_amdgcn_frexp_exp(wave_sum(ch.X));
+    ch.sc = -__builtin_amdgcn_frexp_exp(lanes_sum<64>(ch.X));
   }
   constexpr int dir = FWD ? 1 : -1;
   auto phase = [&](auto combine_tag, int n, int t0) {

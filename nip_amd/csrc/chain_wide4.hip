@@ -23,7 +23,9 @@
 #include <cstdint>
 
 #include "chain_kernels.h"
+#include "mfma_layout.h"
 #include "store_pol.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 
@@ -35,76 +37,9 @@ constexpr int kW4Ring = 16;              // LDS ring depth (steps): two partner 
 constexpr int kW4G = kScratchGuard;
 constexpr int kW4Rescale = 4;            // rescale interval (steps)
 
-template <int K>
-__device__ __forceinline__ double ror(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x120 + K, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x120 + K, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-// x[l] + x[l ^ 16] (pl16) / x[l] + x[l ^ 32] (pl32) in every lane: the swap's
-// second operand is a copy of x made as a whole double (one v_mov_b64; the
-// two results come back in the register pairs of the two operands)
-__device__ __forceinline__ double pl16(double x) {
-  double xc = x;
-  asm("" : "+v"(xc));
-  const auto rl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-__device__ __forceinline__ double pl32(double x) {
-  double xc = x;
-  asm("" : "+v"(xc));
-  const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-
-// fixed-order sum over the wave (identical bits in every lane)
-__device__ __forceinline__ double wave_sum(double x) {
-  asm("" : "+v"(x));       // one rounded value per lane: no fma contraction into the first add
-  x += ror<8>(x);
-  x += ror<4>(x);
-  x += ror<2>(x);
-  x += ror<1>(x);
-  x = pl16(x);
-  x = pl32(x);
-  return x;
-}
-
-// wave_sum of n independent values, stage by stage so their dependency
-// chains interleave
-template <int n>
-__device__ __forceinline__ void wave_sum_n(double (&x)[n]) {
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += ror<8>(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += ror<4>(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += ror<2>(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] += ror<1>(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] = pl16(x[i]);
-#pragma unroll
-  for (int i = 0; i < n; i++) x[i] = pl32(x[i]);
-}
-
-__device__ __forceinline__ double recip(double c) {
-  double r = __builtin_amdgcn_rcp(c);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  return c != 0.0 ? r : 0.0;
-}
-
-__device__ __forceinline__ void block_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // LDS pointers typed as such, so every access is a ds_ instruction (a flat
 // access would also count in vmcnt and serialise on the HBM prefetches)
 typedef __attribute__((address_space(3))) double lds_d;
-typedef double v2d __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v2d lds_v2d;
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
@@ -171,7 +106,7 @@ __device__ __forceinline__ void w4_filter(const WideArgs& a, const W4Lds& L, int
     xb[y] = a.pi[y];
   } else if (nA + nB > 0) {
     const double X = evidence(a, L, T - 1, y) * (y < a.N ? 1.0 : 0.0);   // e_{T-1} o beta_{T-1}
-    sc = -__builtin_amdgcn_frexp_exp(wave_sum(X));
+    sc = -__builtin_amdgcn_frexp_exp(lanes_sum<64>(X));
     xb[y] = X;
   }
   // diagnostics (a.diag): cycles before the barrier, waiting in it, after it
@@ -207,7 +142,7 @@ __device__ __forceinline__ void w4_filter(const WideArgs& a, const W4Lds& L, int
       }
       if (dg) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       stamp(tpre);
-      block_barrier();
+      barrier_lds();
       stamp(twait);
       if (act) {
         const double u = __builtin_ldexp((pb[y] + pb[64 + y]) + (pb[128 + y] + pb[192 + y]), sc);
@@ -219,7 +154,7 @@ __device__ __forceinline__ void w4_filter(const WideArgs& a, const W4Lds& L, int
         }
         const bool rs = (i & (kW4Rescale - 1)) == kW4Rescale - 1 || i == n - 1;
         sc = 0;
-        if (rs) sc = -__builtin_amdgcn_frexp_exp(wave_sum(p));   // frexp exponent of 0 is 0
+        if (rs) sc = -__builtin_amdgcn_frexp_exp(lanes_sum<64>(p));   // frexp exponent of 0 is 0
         xb[y] = p;
       }
       if (dg) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -266,7 +201,7 @@ __device__ __forceinline__ void w4_partner(const WideArgs& a, const W4Lds& L, in
   if (!FWD && !a.filter) Srow[(long)(T - 1) * 64] = y < a.N ? 1.0 : 0.0;   // beta_{T-1}, T-1 >= H
   // phase A: the interface vectors to the scratch
   for (int i = 0; i <= nAi; i++) {
-    block_barrier();
+    barrier_lds();
     const int j = i - 1;
     if (j >= 0 && j < nA) {
       const int slot = j & (kW4Ring - 1);
@@ -291,12 +226,12 @@ __device__ __forceinline__ void w4_partner(const WideArgs& a, const W4Lds& L, in
   auto chunk = [&](const double (&r)[8], int c) {
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-      block_barrier();                               // iteration 8c + k + 1: step 8c + k is in the ring
+      barrier_lds();                               // iteration 8c + k + 1: step 8c + k is in the ring
       const int j = 8 * c + k;
       if (j < nB) {
         const int slot = j & (kW4Ring - 1);
         const double pr = L.ring[(d * kW4Ring + slot) * 64 + y] * (a.filter ? 1.0 : r[k]);
-        const double q = pr * recip(wave_sum(pr));   // an all-zero row stays zero
+        const double q = pr * recip(lanes_sum<64>(pr));   // an all-zero row stays zero
         if (Prow) store_pol<NIPAMD_POST_NT>(Prow + (long)tof(j) * a.post_tstride, q);
         if (FWD) ll_step(slot);
       }
@@ -305,7 +240,7 @@ __device__ __forceinline__ void w4_partner(const WideArgs& a, const W4Lds& L, in
   const int nch = nBi / 8;                           // nBi: a multiple of 8 (kernel)
   double ra[8], rb[8];
   load8(ra, 0);
-  block_barrier();                                   // iteration 0
+  barrier_lds();                                   // iteration 0
   for (int c = 0; c < nch; c += 2) {
     load8(rb, c + 1);
     chunk(ra, c);
@@ -340,79 +275,6 @@ __device__ __forceinline__ void w4_partner(const WideArgs& a, const W4Lds& L, in
 // partner, backward partner (the partners as in chain_wide4_kernel).
 constexpr int kR64Threads = 256;
 
-template <int K, bool NOP_FIRST>
-__device__ __forceinline__ void fmac_b(double& acc, double v, double c) {
-  if (NOP_FIRST)
-    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc) : "v"(v), "v"(c), "n"(K));
-  else
-    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc) : "v"(v), "v"(c), "n"(K));
-}
-
-// acc[j & 3] += x_block(lane j of the row) * Ac[j], j = 0..15 (sixteen
-// accumulators measured slower: 139K vs 128K cycles per block, the extra
-// zeroing and adds cost more issue slots than the shorter chains save; a
-// single wave per SIMD issues f64 VALU work every ~6.3 cycles)
-__device__ __forceinline__ void fmac16(double (&acc)[4], double xb, const double (&Ac)[16]) {
-  fmac_b<0, true>(acc[0], xb, Ac[0]);    fmac_b<1, false>(acc[1], xb, Ac[1]);
-  fmac_b<2, false>(acc[2], xb, Ac[2]);   fmac_b<3, false>(acc[3], xb, Ac[3]);
-  fmac_b<4, false>(acc[0], xb, Ac[4]);   fmac_b<5, false>(acc[1], xb, Ac[5]);
-  fmac_b<6, false>(acc[2], xb, Ac[6]);   fmac_b<7, false>(acc[3], xb, Ac[7]);
-  fmac_b<8, false>(acc[0], xb, Ac[8]);   fmac_b<9, false>(acc[1], xb, Ac[9]);
-  fmac_b<10, false>(acc[2], xb, Ac[10]); fmac_b<11, false>(acc[3], xb, Ac[11]);
-  fmac_b<12, false>(acc[0], xb, Ac[12]); fmac_b<13, false>(acc[1], xb, Ac[13]);
-  fmac_b<14, false>(acc[2], xb, Ac[14]); fmac_b<15, false>(acc[3], xb, Ac[15]);
-}
-
-// the four 16-state blocks of x (lane l holds x(l)) in every lane: xb[b] at
-// lane (row r, i) = x(16 b + i)
-__device__ __forceinline__ void blocks_of(double x, double (&xb)[4]) {
-  // the copies the in-place swaps need, made as whole doubles (one
-  // v_mov_b64 each instead of two v_mov_b32: each swap's two results sit in
-  // the register pairs of its two operands)
-  double xc = x;
-  asm("" : "+v"(xc));
-  const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-  const unsigned clo = (unsigned)__double2loint(xc), chi = (unsigned)__double2hiint(xc);
-  const auto pl = __builtin_amdgcn_permlane16_swap(lo, clo, false, false);   // [0]: block r & ~1, [1]: r | 1
-  const auto ph = __builtin_amdgcn_permlane16_swap(hi, chi, false, false);
-  double p0 = __hiloint2double((int)ph[0], (int)pl[0]), p1 = __hiloint2double((int)ph[1], (int)pl[1]);
-  double p0c = p0, p1c = p1;
-  asm("" : "+v"(p0c));
-  asm("" : "+v"(p1c));
-  const auto q0l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(p0), (unsigned)__double2loint(p0c), false, false);
-  const auto q0h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(p0), (unsigned)__double2hiint(p0c), false, false);
-  const auto q1l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(p1), (unsigned)__double2loint(p1c), false, false);
-  const auto q1h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(p1), (unsigned)__double2hiint(p1c), false, false);
-  xb[0] = __hiloint2double((int)q0h[0], (int)q0l[0]);
-  xb[2] = __hiloint2double((int)q0h[1], (int)q0l[1]);
-  xb[1] = __hiloint2double((int)q1h[0], (int)q1l[0]);
-  xb[3] = __hiloint2double((int)q1h[1], (int)q1l[1]);
-}
-
-// The rescale exponent from the largest element instead of the sum: any
-// power of two serves (the ring's vectors and the partners' sums carry it
-// exactly, posteriors and ll are scale-free), and an integer max over the
-// wave is 32-bit DPP work (about 16 instructions) where the f64 wave sum was
-// 43.  Zeros do not count; an all-zero vector keeps the scale (-> 0).
-__device__ __forceinline__ int max_exp_rescale(double p) {
-  int e = p != 0.0 ? __builtin_amdgcn_frexp_exp(p) : -0x40000;
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x128, 0xF, 0xF, true));   // row_ror:8
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x124, 0xF, 0xF, true));   // row_ror:4
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x122, 0xF, 0xF, true));   // row_ror:2
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x121, 0xF, 0xF, true));   // row_ror:1
-  {
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)e, (unsigned)e, false, false);
-    e = max((int)r[0], (int)r[1]);
-  }
-  {
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)e, (unsigned)e, false, false);
-    e = max((int)r[0], (int)r[1]);
-  }
-  return e > -0x40000 ? -e : 0;
-}
-
 // NC: observed columns (0..4).  The step's evidence e_t(y) = ebase(y) x one
 // table entry per column: the codes of the next 8 steps are read a chunk
 // ahead and each entry one step ahead, so no LDS load waits on the
@@ -445,7 +307,7 @@ __device__ __forceinline__ void r64_filter(const WideArgs& a, const W4Lds& L, in
     x = a.pi[y];
   } else {
     x = (nA + nB > 0) ? evidence(a, L, T - 1, y) * (y < a.N ? 1.0 : 0.0) : 0.0;   // e_{T-1} o beta_{T-1}
-    sc = -__builtin_amdgcn_frexp_exp(wave_sum(x));
+    sc = -__builtin_amdgcn_frexp_exp(lanes_sum<64>(x));
   }
   const double eb = L.tab[L.eoff + y];
   const int toff[4] = {L.toff0, L.toff1, L.toff2, L.toff3};
@@ -486,7 +348,7 @@ __device__ __forceinline__ void r64_filter(const WideArgs& a, const W4Lds& L, in
     // one step i (j = i mod 8, the unrolled position; rs: rescale after it)
     auto step = [&](int i, int j, bool rs) {
       double xb[4];
-      blocks_of(x, xb);
+      seq_blocks<4>(x, xb);
       double acc[4] = {0.0, 0.0, 0.0, 0.0};
       fmac16(acc, xb[0], Ac[0]);
       fmac16(acc, xb[1], Ac[1]);
@@ -500,7 +362,7 @@ __device__ __forceinline__ void r64_filter(const WideArgs& a, const W4Lds& L, in
       const int slot = i & (kW4Ring - 1);
       L.ring[(d * kW4Ring + slot) * 64 + y] = FWD ? p : u;
       if (FWD) L.uring[slot * 64 + y] = u;
-      sc = rs ? max_exp_rescale(p) : 0;
+      sc = rs ? max_exp_rescale<64>(p) : 0;
       x = p;
     };
     for (int c = 0; c < ni; c += 8) {
@@ -528,7 +390,7 @@ __device__ __forceinline__ void r64_filter(const WideArgs& a, const W4Lds& L, in
       }
       const unsigned long long tb = dg ? __builtin_readcyclecounter() : 0;
       if (NIPAMD_R64_SOLO == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      else block_barrier();                             // the chunk to the partner
+      else barrier_lds();                             // the chunk to the partner
       if (dg) twait += __builtin_readcyclecounter() - tb;
     }
   };
@@ -537,7 +399,7 @@ __device__ __forceinline__ void r64_filter(const WideArgs& a, const W4Lds& L, in
   if (NIPAMD_R64_SOLO != 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // phase barrier
   // phase B: forward alpha_H..alpha_{T-1}; backward beta_{H-1}..beta_0
   phase(nB, nBi, 1);
-  if (NIPAMD_R64_SOLO != 1) block_barrier();            // the partners' ll hand-over
+  if (NIPAMD_R64_SOLO != 1) barrier_lds();            // the partners' ll hand-over
   if (dg && y == 0) {
     a.diag[blockIdx.x * 16 + (FWD ? 0 : 4) + 0] = __builtin_readcyclecounter() - c0;
     a.diag[blockIdx.x * 16 + (FWD ? 0 : 4) + 1] = twait;
@@ -571,13 +433,13 @@ __device__ __forceinline__ void r64_partner(const WideArgs& a, const W4Lds& L, i
   if (!FWD && !a.filter) Srow[(long)(T - 1) * 64] = y < a.N ? 1.0 : 0.0;   // beta_{T-1}, T-1 >= H
   // phase A: the interface vectors to the scratch
   for (int c = 0; c < nAi; c += 8) {
-    block_barrier();
+    barrier_lds();
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int j = c + k;
       const int slot = j & (kW4Ring - 1);
       if (j < nA) store_pol<NIPAMD_WIDE_SCR_NT>(Srow + (long)(FWD ? j : T - 2 - j) * 64, (double)L.ring[(d * kW4Ring + slot) * 64 + y]);
-      if (j < nAf) ll_acc(wave_sum(zval(slot)));
+      if (j < nAf) ll_acc(lanes_sum<64>(zval(slot)));
     }
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // phase barrier
@@ -594,7 +456,7 @@ __device__ __forceinline__ void r64_partner(const WideArgs& a, const W4Lds& L, i
     for (int k = 0; k < 8; k++) r[k] = load_pol<NIPAMD_SCR_NTLD>(Sld + (long)tof(8 * c + k) * sstr);   // guards cover the over-run
   };
   auto chunk = [&](const double (&r)[8], int c) {
-    block_barrier();                                 // the filter's chunk c is in the ring
+    barrier_lds();                                 // the filter's chunk c is in the ring
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int j = 8 * c + k;
@@ -627,7 +489,7 @@ __device__ __forceinline__ void r64_partner(const WideArgs& a, const W4Lds& L, i
     L.xb[0] = m;
     L.xb[1] = (double)e;
   }
-  block_barrier();
+  barrier_lds();
   if (FWD && y == 0) {
     const double m1 = L.xb[0];
     const int e1 = (int)L.xb[1];
@@ -711,10 +573,10 @@ void chain_wide4_kernel(WideArgs a) {
     else if (NIPAMD_R64_SOLO == 1) return;
     else if (NIPAMD_R64_SOLO == 2) {
       // the partners' barriers only (the filters' chunk, phase and closing ones)
-      for (int c = 0; c < nAi; c += 8) block_barrier();
+      for (int c = 0; c < nAi; c += 8) barrier_lds();
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      for (int c = 0; c < nBi; c += 8) block_barrier();
-      block_barrier();
+      for (int c = 0; c < nBi; c += 8) barrier_lds();
+      barrier_lds();
     }
     else if (wave == 2) r64_partner<true>(a, L, lane, b, nAf, nAi, nBf, nBi, nAf, nBf);
     else r64_partner<false>(a, L, lane, b, nAb, nAi, nBb, nBi, nAf, nBf);

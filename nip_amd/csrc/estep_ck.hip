@@ -76,15 +76,11 @@ __host__ __device__ inline int ck_et_doubles(int R) { return (R * kCkEt + 1) & ~
 __host__ __device__ inline int ck_count(int T) { return (T + 3) >> 2; }
 __host__ __device__ inline long ck_group_doubles(int T) { return (long)ck_count(T) * (256 + 8); }
 
-// transpose buffer [row][16]: the 16-byte piece p of row r at (p ^ (r & 7)):
-// the filter-layout writes (lane (g, j): pieces g and g + 4 of row j) and the
-// sequence-major reads (a row's 16 doubles per 16 lanes) are conflict-free
-__device__ __forceinline__ int tp_off(int row, int piece) { return row * 16 + ((piece ^ (row & 7)) << 1); }
-
+// transpose buffer [row][16], its pieces swizzled by piece_off<16>:
 // filter layout (lane (g, j): states 2g, 2g+1, 2g+8, 2g+9 of sequence j) -> row j
 __device__ __forceinline__ void tp_write(double* buf, int j, int g, const v4d& v) {
-  *reinterpret_cast<v2d*>(buf + tp_off(j, g)) = v2d{v.x, v.y};
-  *reinterpret_cast<v2d*>(buf + tp_off(j, g + 4)) = v2d{v.z, v.w};
+  *reinterpret_cast<v2d*>(buf + piece_off<16>(j, g)) = v2d{v.x, v.y};
+  *reinterpret_cast<v2d*>(buf + piece_off<16>(j, g + 4)) = v2d{v.z, v.w};
 }
 
 // sequence-major: lane l gets state l & 15 of sequences 4q + (l >> 4), q = 0..3 --
@@ -94,10 +90,10 @@ __device__ __forceinline__ v4d tp_read(const double* buf, int lane) {
   const int y = lane & 15, k = lane >> 4;
   const int p = y >> 1, e = y & 1;
   v4d r;
-  r.x = buf[tp_off(k, p) + e];
-  r.y = buf[tp_off(4 + k, p) + e];
-  r.z = buf[tp_off(8 + k, p) + e];
-  r.w = buf[tp_off(12 + k, p) + e];
+  r.x = buf[piece_off<16>(k, p) + e];
+  r.y = buf[piece_off<16>(4 + k, p) + e];
+  r.z = buf[piece_off<16>(8 + k, p) + e];
+  r.w = buf[piece_off<16>(12 + k, p) + e];
   return r;
 }
 
@@ -108,8 +104,6 @@ __device__ __forceinline__ v4d mfma4(const v4d& a, const v4d& b, v4d d) {
   d = __builtin_amdgcn_mfma_f64_16x16x4f64(a.w, b.w, d, 0, 0, 0);
   return d;
 }
-
-__device__ __forceinline__ unsigned byte_of(unsigned w, int k) { return (w >> (8 * k)) & 0xFFu; }
 
 #ifndef NIPAMD_CK_LDS_ADD
 #define NIPAMD_CK_LDS_ADD 1                  // A/B builds: 0 = read-add-write
@@ -463,7 +457,7 @@ __global__ __launch_bounds__(kCkThreads, 2) void chain_estep_ck_kernel(ChainArgs
   const v4d q0 = p0 * recip(chain_sum(p0));
   tp_write(XG, j, g, q0);
   const v4d q0T = tp_read(XG, lane);
-  const double p0s = sum_lanes16(sum_lanes32((q0T.x + q0T.y) + (q0T.z + q0T.w)));
+  const double p0s = xor16_sum(xor32_sum((q0T.x + q0T.y) + (q0T.z + q0T.w)));
 
   // the slab row (chain_estep_slab layout)
   double* slab = a.counts + (size_t)grp * chain_estep_slab(M);

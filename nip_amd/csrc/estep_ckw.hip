@@ -55,12 +55,6 @@ __host__ __device__ inline int ckw_count(int T) { return (T + 3) >> 2; }
 // checkpoints per group: [nck][16][32] doubles, then [nck][16] int exponents
 __host__ __device__ inline long ckw_group_doubles(int T) { return (long)ckw_count(T) * (16 * NP + 8); }
 
-__device__ __forceinline__ unsigned byte_of4(unsigned w, int k) { return (w >> (8 * k)) & 0xFFu; }
-
-__device__ __forceinline__ v4d mfma1(double a, double b, v4d d) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, d, 0, 0, 0);
-}
-
 // the mat-vec of the fb kernels at NT = 2 (chain_mfma_wide.hip): d[qo] =
 // sum over the input tiles qi; the two output tiles' chains interleaved
 __device__ __forceinline__ void matvec2(const double (&Aop)[NT][NT][4], const v4d (&X)[NT], v4d (&d)[NT]) {
@@ -68,14 +62,14 @@ __device__ __forceinline__ void matvec2(const double (&Aop)[NT][NT][4], const v4
   d[1] = v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int qi = 0; qi < NT; qi++) {
-    d[0] = mfma1(Aop[0][qi][0], X[qi].x, d[0]);
-    d[1] = mfma1(Aop[1][qi][0], X[qi].x, d[1]);
-    d[0] = mfma1(Aop[0][qi][1], X[qi].y, d[0]);
-    d[1] = mfma1(Aop[1][qi][1], X[qi].y, d[1]);
-    d[0] = mfma1(Aop[0][qi][2], X[qi].z, d[0]);
-    d[1] = mfma1(Aop[1][qi][2], X[qi].z, d[1]);
-    d[0] = mfma1(Aop[0][qi][3], X[qi].w, d[0]);
-    d[1] = mfma1(Aop[1][qi][3], X[qi].w, d[1]);
+    d[0] = mfma(Aop[0][qi][0], X[qi].x, d[0]);
+    d[1] = mfma(Aop[1][qi][0], X[qi].x, d[1]);
+    d[0] = mfma(Aop[0][qi][1], X[qi].y, d[0]);
+    d[1] = mfma(Aop[1][qi][1], X[qi].y, d[1]);
+    d[0] = mfma(Aop[0][qi][2], X[qi].z, d[0]);
+    d[1] = mfma(Aop[1][qi][2], X[qi].z, d[1]);
+    d[0] = mfma(Aop[0][qi][3], X[qi].w, d[0]);
+    d[1] = mfma(Aop[1][qi][3], X[qi].w, d[1]);
   }
 }
 
@@ -94,7 +88,7 @@ __device__ __forceinline__ void matvec2_lds(const double* Al, int lane, const v4
 
 // sum of a sequence's 32 states (its two tiles in the sequence's 4 lanes)
 __device__ __forceinline__ double seq_sum(const v4d (&v)[NT]) {
-  return sum_lanes16(sum_lanes32(((v[0].x + v[0].y) + (v[0].z + v[0].w)) + ((v[1].x + v[1].y) + (v[1].z + v[1].w))));
+  return xor16_sum(xor32_sum(((v[0].x + v[0].y) + (v[0].z + v[0].w)) + ((v[1].x + v[1].y) + (v[1].z + v[1].w))));
 }
 
 // transpose row j (16 sequences x NPS doubles): filter layout (lane (g, j):
@@ -212,11 +206,11 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
   // carries the unobserved children's row sums)
   auto evid = [&](const unsigned (&w)[NC], int k, v4d (&e)[NT]) {
 #pragma unroll
-    for (int q = 0; q < NT; q++) e[q] = load4(tab + toff[0] + (int)byte_of4(w[0], k) * NPS + 16 * q);
+    for (int q = 0; q < NT; q++) e[q] = load4(tab + toff[0] + (int)byte_of(w[0], k) * NPS + 16 * q);
 #pragma unroll
     for (int c = 1; c < NC; c++)
 #pragma unroll
-      for (int q = 0; q < NT; q++) e[q] *= load4(tab + toff[c] + (int)byte_of4(w[c], k) * NPS + 16 * q);
+      for (int q = 0; q < NT; q++) e[q] *= load4(tab + toff[c] + (int)byte_of(w[c], k) * NPS + 16 * q);
   };
 
   double Af[NT][NT][4], Ab[NT][NT][4];
@@ -489,7 +483,7 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
     if constexpr (!POST) {
 #pragma unroll
       for (int h = 0; h < 2; h++)
-        AD[(g * 2 + h) * 16 + j] = (h < NC ? cro[h] + (int)byte_of4(wc[h < NC ? h : 0], g) : crows) * NP;
+        AD[(g * 2 + h) * 16 + j] = (h < NC ? cro[h] + (int)byte_of(wc[h < NC ? h : 0], g) : crows) * NP;
     }
     v4d x[NT] = {Cr[0], Cr[1]};                  // chunk c - 1's recomputation chain
     v4d nV[VL ? 1 : 3][NT];
@@ -531,7 +525,7 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
 #pragma unroll
         for (int xt = 0; xt < NT; xt++)
 #pragma unroll
-          for (int yt = 0; yt < NT; yt++) Kd[xt][yt] = mfma1(aT[xt][q], wT[yt][q], Kd[xt][yt]);
+          for (int yt = 0; yt < NT; yt++) Kd[xt][yt] = mfma(aT[xt][q], wT[yt][q], Kd[xt][yt]);
       // count rows: one add per sequence (lanes 0-31 column 0's row, 32-63
       // column 1's); every operand read before the first add, so the adds
       // (which the compiler must order against later LDS reads) cost one wait
@@ -614,7 +608,7 @@ __global__ __launch_bounds__(VL ? 512 : kWThreads, 1) void chain_estep_ckw_kerne
     tp_write2(XA, j, g, p0);
     tp_read2(XA, lane, r);
 #pragma unroll
-    for (int xt = 0; xt < NT; xt++) p0s[xt] = sum_lanes16(sum_lanes32((r[xt][0] + r[xt][1]) + (r[xt][2] + r[xt][3])));
+    for (int xt = 0; xt < NT; xt++) p0s[xt] = xor16_sum(xor32_sum((r[xt][0] + r[xt][1]) + (r[xt][2] + r[xt][3])));
   }
 
   // the slab row: K [32][32], H [R][32], P0 [32]

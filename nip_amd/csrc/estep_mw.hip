@@ -56,14 +56,13 @@
 #include <cstdint>
 
 #include "chain_kernels.h"
+#include "mfma_layout.h"
 #include "store_pol.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double v2d __attribute__((ext_vector_type(2)));
 
 constexpr int kSeq = 16;               // sequences (chains) per group
 constexpr int kGroups = 2;             // groups per block
@@ -79,66 +78,12 @@ constexpr int kMaxMT = 4;              // matrix-core count-row tiles: sum of th
 constexpr int kPass = kSeq / 2;
 constexpr int kMaxCols = 2;            // evidence columns the kernel takes        // partner passes per chunk: two chains x CH steps x 16 lanes each
 
-__host__ __device__ constexpr int state_of(int g, int r) { return r < 2 ? 2 * g + r : 6 + 2 * g + r; }
-// chain j's piece p (states 2p, 2p + 1) within a ring row, XOR-swizzled by j & 7
-__device__ __forceinline__ int piece_off(int j, int p) { return j * NP + ((p ^ (j & 7)) << 1); }
-
-__device__ __forceinline__ double swap32_sum(double x) {     // x[l] + x[l ^ 32]
-  double xc = x;
-  asm("" : "+v"(xc));
-  const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-__device__ __forceinline__ double swap16_sum(double x) {     // x[l] + x[l ^ 16]
-  double xc = x;
-  asm("" : "+v"(xc));
-  const auto rl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
 // the four lanes l, l ^ 16, l ^ 32, l ^ 48 (a chain's lanes in the filter
 // layout, a state pair's lanes in the partner layout): identical bits in all
 __device__ __forceinline__ double quad_sum(double x) {
   asm("" : "+v"(x));        // one rounded value per lane: no fma contraction into the first add
-  return swap16_sum(swap32_sum(x));
+  return xor16_sum(xor32_sum(x));
 }
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// sum over the 16 lanes of a DPP row (identical bits in all of them)
-__device__ __forceinline__ double row_sum16(double x) {
-  asm("" : "+v"(x));
-  x += dpp64<0xB1>(x);      // quad_perm [1,0,3,2]
-  x += dpp64<0x4E>(x);      // quad_perm [2,3,0,1]
-  x += dpp64<0x141>(x);     // row_half_mirror
-  x += dpp64<0x140>(x);     // row_mirror
-  return x;
-}
-__device__ __forceinline__ double recip(double c) {
-  double r = __builtin_amdgcn_rcp(c);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  return c != 0.0 ? r : 0.0;
-}
-__device__ __forceinline__ v4d ldexp4(v4d v, int k) {
-  v4d r;
-  r.x = __builtin_ldexp(v.x, k); r.y = __builtin_ldexp(v.y, k);
-  r.z = __builtin_ldexp(v.z, k); r.w = __builtin_ldexp(v.w, k);
-  return r;
-}
-__device__ __forceinline__ v4d load4(const double* p) {      // p = row + 16q + 2g
-  const v2d a = *reinterpret_cast<const v2d*>(p);
-  const v2d b = *reinterpret_cast<const v2d*>(p + 8);
-  return v4d{a.x, a.y, b.x, b.y};
-}
-__device__ __forceinline__ v4d mfma(double a, double b, v4d d) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, d, 0, 0, 0);
-}
-__device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void barrier_phase() {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
@@ -198,7 +143,7 @@ struct EFilter {
 #pragma unroll
     for (int k = 0; k < NC; k++)
 #pragma unroll
-      for (int q = 0; q < NT; q++) r[k][q] = load4(c.tab + c.tab_off[k] + cd[k] * NPS + 16 * q);
+      for (int q = 0; q < NT; q++) r[k][q] = load4v(c.tab + c.tab_off[k] + cd[k] * NPS + 16 * q);
   }
   __device__ __forceinline__ void product(const v4d (&r)[NC][NT], v4d (&e)[NT]) const {
 #pragma unroll
@@ -338,8 +283,8 @@ __device__ __forceinline__ void efilter(const EMwArgs& a, const FCtx& c, int lan
     double py = 0.0;
 #pragma unroll
     for (int q = 0; q < NT; q++) {
-      f.X[q] = load4(a.pi + 16 * q + 2 * g);
-      f.wv[q] = load4(a.w + 16 * q + 2 * g);
+      f.X[q] = load4v(a.pi + 16 * q + 2 * g);
+      f.wv[q] = load4v(a.w + 16 * q + 2 * g);
       py += (f.X[q].x * f.wv[q].x + f.X[q].y * f.wv[q].y) + (f.X[q].z * f.wv[q].z + f.X[q].w * f.wv[q].w);
     }
     f.m1 = quad_sum(py);                   // y_{-1} = prior . w
@@ -432,7 +377,7 @@ __device__ __forceinline__ void epartner(const EMwArgs& a, double* ring, int* re
 #pragma unroll
       for (int u0 = 0; u0 < kSeq * NP / 2; u0 += 64) {
         const int u = u0 + lane, jj = u >> 4, p = u & 15;
-        const v2d v = *reinterpret_cast<const v2d*>(slot + (k + 1) * kStep + piece_off(jj, p));
+        const v2d v = *reinterpret_cast<const v2d*>(slot + (k + 1) * kStep + piece_off<NP>(jj, p));
         store_pol<NIPAMD_WIDE_SCR_NT>(reinterpret_cast<v2d*>(Sblk + t * kStep + 2 * u), v);
       }
       if (lane < kSeq) Eblk[t * kSeq + lane] = es[(k + 1) * kRowI + lane];
@@ -502,8 +447,8 @@ __device__ __forceinline__ void epartner(const EMwArgs& a, double* ring, int* re
 #pragma unroll
       for (int qp = 0; qp < kPass; qp++) {
         const int j = 2 * qp + c2;
-        const v2d m = *reinterpret_cast<const v2d*>(slot + kStep + piece_off(j, s));
-        const double cs = row_sum16(m.x * P.o[qp].x + m.y * P.o[qp].y);
+        const v2d m = *reinterpret_cast<const v2d*>(slot + kStep + piece_off<NP>(j, s));
+        const double cs = mirror_sum<16>(m.x * P.o[qp].x + m.y * P.o[qp].y);
         if (hi == 0 && s == 0) {
           const bool live = b0 + j < a.B;
           cz[2 * j] = live ? recip(cs) : 0.0;
@@ -515,8 +460,8 @@ __device__ __forceinline__ void epartner(const EMwArgs& a, double* ring, int* re
     for (int qp = 0; qp < kPass; qp++) {
       const int j = 2 * qp + c2;
       const bool live = valid && b0 + j < a.B;
-      const v2d mc = *reinterpret_cast<const v2d*>(slot + (hi + 1) * kStep + piece_off(j, s));
-      const v2d ma = *reinterpret_cast<const v2d*>(slot + hi * kStep + piece_off(j, s));
+      const v2d mc = *reinterpret_cast<const v2d*>(slot + (hi + 1) * kStep + piece_off<NP>(j, s));
+      const v2d ma = *reinterpret_cast<const v2d*>(slot + hi * kStep + piece_off<NP>(j, s));
       const int Ec = es[(hi + 1) * kRowI + j], Ea = es[hi * kRowI + j];
       // raw codes at this step (row hi + 1) and at its neighbour (row hi:
       // backward, t + 1, whose evidence w takes)
@@ -725,8 +670,8 @@ __global__ __launch_bounds__(kThreads, 1) void chain_estep_mw_kernel(EMwArgs a) 
   c.g = g;
 #pragma unroll
   for (int q = 0; q < NT; q++) {
-    c.wo[q][0] = piece_off(j, 8 * q + g);
-    c.wo[q][1] = piece_off(j, 8 * q + 4 + g);
+    c.wo[q][0] = piece_off<NP>(j, 8 * q + g);
+    c.wo[q][1] = piece_off<NP>(j, 8 * q + 4 + g);
   }
   if (fwd) efilter<true, NC>(a, c, lane, b0, nchA, nchB);
   else efilter<false, NC>(a, c, lane, b0, nchA, nchB);

@@ -43,63 +43,19 @@
 #include <type_traits>
 
 #include "chain_kernels.h"
-#include "dpp_row.h"
+#include "mfma_layout.h"
 #include "opchain.h"
 #include "store_pol.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 constexpr int kMsgWaves = 4;                 // 2 forward + 2 backward (no LDS: blocks just group waves)
 constexpr int kMsgChunk = 8;                 // steps of evidence prefetched ahead
 constexpr int kStatSeqs = 16;                // sequences per stats block (one slab row)
 constexpr int kStatWaves = 4;
-
-template <int K>
-__device__ __forceinline__ double rorK(double v) {     // row_ror:K of a double (16-lane rows)
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x120 + K, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x120 + K, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// x[l ^ 16] + x[l] in both lanes: the pair's sum (the swap's second operand
-// a copy of x made as a whole double: one v_mov_b64)
-__device__ __forceinline__ double swap16(double x) {
-  double xc = x;
-  asm("" : "+v"(xc));
-  const auto rl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-__device__ __forceinline__ double swap32(double x) {
-  double xc = x;
-  asm("" : "+v"(xc));
-  const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-  const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-  return __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-}
-// sum over aligned groups of L lanes (16, 32 or 64); every level pairs equal
-// partial sums, so all L lanes end with the same bits
-template <int L>
-__device__ __forceinline__ double group_sum(double x) {
-  asm("" : "+v"(x));       // one rounded value per lane: no fma contraction into the first add
-  x += rorK<8>(x);
-  x += rorK<4>(x);
-  x += rorK<2>(x);
-  x += rorK<1>(x);
-  if (L >= 32) x = swap16(x);
-  if (L >= 64) x = swap32(x);
-  return x;
-}
-
-__device__ __forceinline__ double recip(double c) {
-  double r = __builtin_amdgcn_rcp(c);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  r = __builtin_fma(r, __builtin_fma(-c, r, 1.0), r);
-  return c != 0.0 ? r : 0.0;
-}
 
 // child c's code at step t: its state, M missing, M + 1 out of range
 
@@ -109,55 +65,6 @@ __device__ __forceinline__ double evidence(const EWideArgs& a, const int* o, int
   double e = a.ebase[y];
   for (int c = 0; c < a.ncol; c++) e *= a.tab[a.tab_off[c] + code_of(o[a.col[c]], a.M[c]) * 64 + y];
   return e;
-}
-
-// acc[j & 3] += x(lane j of the row) * Ac[j], j = 0..15 (four chains, the
-// broadcast by DPP row_newbcast, as chain_row64_kernel does)
-__device__ __forceinline__ void fmac16(double (&acc)[4], double xb, const double (&Ac)[16]) {
-  fmac_bcast<0, true>(acc[0], xb, Ac[0]);    fmac_bcast<1, false>(acc[1], xb, Ac[1]);
-  fmac_bcast<2, false>(acc[2], xb, Ac[2]);   fmac_bcast<3, false>(acc[3], xb, Ac[3]);
-  fmac_bcast<4, false>(acc[0], xb, Ac[4]);   fmac_bcast<5, false>(acc[1], xb, Ac[5]);
-  fmac_bcast<6, false>(acc[2], xb, Ac[6]);   fmac_bcast<7, false>(acc[3], xb, Ac[7]);
-  fmac_bcast<8, false>(acc[0], xb, Ac[8]);   fmac_bcast<9, false>(acc[1], xb, Ac[9]);
-  fmac_bcast<10, false>(acc[2], xb, Ac[10]); fmac_bcast<11, false>(acc[3], xb, Ac[11]);
-  fmac_bcast<12, false>(acc[0], xb, Ac[12]); fmac_bcast<13, false>(acc[1], xb, Ac[13]);
-  fmac_bcast<14, false>(acc[2], xb, Ac[14]); fmac_bcast<15, false>(acc[3], xb, Ac[15]);
-}
-
-// the NB = NP / 16 blocks of 16 states of this lane's sequence, each in
-// every lane of the sequence's rows: xb[b](lane 16 r + j) = x(state 16 b + j).
-// One row per sequence (NB 1): x itself; two rows (NB 2): one
-// v_permlane16_swap per half ([0]: the pair's even row, [1]: its odd row);
-// four rows (NB 4): a v_permlane32_swap level on both results.
-template <int NB>
-__device__ __forceinline__ void seq_blocks(double x, double (&xb)[NB]) {
-  if constexpr (NB == 1) {
-    xb[0] = x;
-  } else {
-    // the swaps' second operands are copies made as whole doubles (one
-    // v_mov_b64 each)
-    double xc = x;
-    asm("" : "+v"(xc));
-    const auto pl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(xc), false, false);
-    const auto ph = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(xc), false, false);
-    if constexpr (NB == 2) {
-      xb[0] = __hiloint2double((int)ph[0], (int)pl[0]);
-      xb[1] = __hiloint2double((int)ph[1], (int)pl[1]);
-    } else {
-      double p0 = __hiloint2double((int)ph[0], (int)pl[0]), p1 = __hiloint2double((int)ph[1], (int)pl[1]);
-      double p0c = p0, p1c = p1;
-      asm("" : "+v"(p0c));
-      asm("" : "+v"(p1c));
-      const auto q0l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(p0), (unsigned)__double2loint(p0c), false, false);   // blocks 0, 2
-      const auto q0h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(p0), (unsigned)__double2hiint(p0c), false, false);
-      const auto q1l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(p1), (unsigned)__double2loint(p1c), false, false);   // blocks 1, 3
-      const auto q1h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(p1), (unsigned)__double2hiint(p1c), false, false);
-      xb[0] = __hiloint2double((int)q0h[0], (int)q0l[0]);
-      xb[2] = __hiloint2double((int)q0h[1], (int)q0l[1]);
-      xb[1] = __hiloint2double((int)q1h[0], (int)q1l[0]);
-      xb[3] = __hiloint2double((int)q1h[1], (int)q1l[1]);
-    }
-  }
 }
 
 // u(y) = sum_x Ac[x / 16][x % 16] x(x) over this lane's sequence: NP
@@ -170,27 +77,6 @@ __device__ __forceinline__ double matvec_dpp(double x, const double (&Ac)[NB][16
 #pragma unroll
   for (int b = 0; b < NB; b++) fmac16(acc, xb[b], Ac[b]);
   return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-
-// the rescale exponent of a proper model's forward filter: minus the largest
-// binary exponent over the sequence's NP lanes (zeros excluded; 0 for an
-// all-zero vector), integer DPP / permlane work instead of an f64 sum
-template <int NP>
-__device__ __forceinline__ int group_max_exp_rescale(double p) {
-  int e = p != 0.0 ? __builtin_amdgcn_frexp_exp(p) : -0x40000;
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x128, 0xF, 0xF, true));   // row_ror:8
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x124, 0xF, 0xF, true));   // row_ror:4
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x122, 0xF, 0xF, true));   // row_ror:2
-  e = max(e, __builtin_amdgcn_mov_dpp(e, 0x121, 0xF, 0xF, true));   // row_ror:1
-  if (NP >= 32) {
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)e, (unsigned)e, false, false);
-    e = max((int)r[0], (int)r[1]);
-  }
-  if (NP >= 64) {
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)e, (unsigned)e, false, false);
-    e = max((int)r[0], (int)r[1]);
-  }
-  return e > -0x40000 ? -e : 0;
 }
 
 // PR: a proper model (EWideArgs::proper): the forward filter keeps no step
@@ -270,10 +156,10 @@ __global__ __launch_bounds__(kMsgWaves * 64) void chain_msgs_kernel(EWideArgs a)
           if (y == 0) Ea[t] = E;
         }
         if (PR) {
-          sc = group_max_exp_rescale<NP>(p);
+          sc = max_exp_rescale<NP>(p);
         } else {
-          const double z2 = group_sum<NP>(p);
-          const double z1 = group_sum<NP>(u * sy);
+          const double z2 = lanes_sum<NP>(p);
+          const double z1 = lanes_sum<NP>(u * sy);
           zmin = __builtin_fmin(zmin, z2);
           // renormalised at every step: the route serves the e_steps below
           // the step-shrink bound, where four steps' masses leave fp64
@@ -288,7 +174,7 @@ __global__ __launch_bounds__(kMsgWaves * 64) void chain_msgs_kernel(EWideArgs a)
       for (int k = 0; k < kMsgChunk; k++) e[k] = en[k];
     }
     // proper: ll = log(sum alpha^_{T-1}) - E_{T-1} ln 2 (x = alpha^_{T-1})
-    const double zT = PR ? group_sum<NP>(x) : 0.0;
+    const double zT = PR ? lanes_sum<NP>(x) : 0.0;
     if (active && y == 0) {
       double ll = PR ? log(zT) - (double)E * 0.69314718055994530942
                      : log(m2) - log(m1) + (double)(e2 - e1) * 0.69314718055994530942;
@@ -311,7 +197,7 @@ __global__ __launch_bounds__(kMsgWaves * 64) void chain_msgs_kernel(EWideArgs a)
         const int t = T - 1 - (j0 + k);
         if (t < 0) break;
         const double g = e[k] * xbeta;
-        const double z = group_sum<NP>(g);
+        const double z = lanes_sum<NP>(g);
         const int sc = z != 0.0 ? -__builtin_amdgcn_frexp_exp(z) : 0;
         const double u = __builtin_ldexp(matvec_dpp<NB>(g, Ac), sc);
         if (active) Sb[(size_t)t * NP] = u;
@@ -321,12 +207,6 @@ __global__ __launch_bounds__(kMsgWaves * 64) void chain_msgs_kernel(EWideArgs a)
       for (int k = 0; k < kMsgChunk; k++) e[k] = en[k];
     }
   }
-}
-
-// One 16x16x4 f64 MFMA: D += A (16 x 4) B (4 x 16); lane l supplies
-// A[l & 15][l >> 4] and B[l >> 4][l & 15], and holds D[(l >> 4) + 4 r][l & 15].
-__device__ __forceinline__ v4d mfma(double a, double b, v4d d) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, d, 0, 0, 0);
 }
 
 // the children's evidence tables [(M_k + 2)][64] and ebase [64], staged in
@@ -410,7 +290,7 @@ __global__ __launch_bounds__(kStatWaves * 64, 1) void chain_stats_kernel(EWideAr
       const double* Sb = a.Sb + (size_t)(b0 + sq) * (T + 1) * NP;
       const int x = lane < NP ? lane : 0;
       const double v = (lane < NP && x < N) ? a.pi[x] * Sb[x] : 0.0;
-      const double z = group_sum<64>(v);
+      const double z = lanes_sum<64>(v);
       p0 += v * recip(z);
     }
     const bool ok = t0 + k4 < T;
@@ -428,7 +308,7 @@ __global__ __launch_bounds__(kStatWaves * 64, 1) void chain_stats_kernel(EWideAr
     double zz = 0.0;
 #pragma unroll
     for (int q = 0; q < NT; q++) { pr[q] = cur.al[q] * cur.be[q]; zz += pr[q]; }
-    const double c = group_sum<16>(zz);
+    const double c = lanes_sum<16>(zz);
     const double rc = ok ? recip(c) : 0.0;
     const double f = __builtin_ldexp(rc, cur.ef);
     double w[NT], g[NT];
@@ -721,12 +601,12 @@ __global__ __launch_bounds__(MsgCfg<NP>::waves * 64) __attribute__((amdgpu_waves
       const int j = j0 + k;
       if (j >= n) break;
       const int t = t0 + dir * j;
-      const double m1v = fwd ? group_sum<NP>(x * wy) : 0.0;
+      const double m1v = fwd ? lanes_sum<NP>(x * wy) : 0.0;
       const double acc = matvec_dpp<NB>(fwd ? x : x * ec[k], C);
       coef(k + 1 < kOpMsgChunk ? cc[k + 1] : cn[0], C);   // the next step's operator, under this step's work
       double u = ys ? __builtin_ldexp(acc, sc) : 0.0;
       if (fwd) u *= ec[k];
-      const double z = group_sum<NP>(u);
+      const double z = lanes_sum<NP>(u);
       if (fwd) {
         if (cc[k] & kOpEv) {                            // a step with evidence
           m2 *= z;
@@ -774,7 +654,7 @@ __global__ __launch_bounds__(256) void op_wide_post_kernel(OpWideArgs a) {
   const long r = ok ? row : 0;
   const double al = a.Sa[(size_t)r * NP + y];
   const double pr = a.filter ? al : al * a.Sb[(size_t)r * NP + y];
-  const double z = group_sum<NP>(pr);
+  const double z = lanes_sum<NP>(pr);
   const double q = z != 0.0 ? pr / z : pr;
   if (ok && y < a.K) {
     const long b = r / a.T, t = r - b * a.T;
@@ -1052,7 +932,7 @@ __global__ __launch_bounds__(kXwThreads) __attribute__((amdgpu_waves_per_eu(XiCf
       for (int q = 0; q < SL; q++) {
         const int jj = wave * (kXwBatch / kXwWaves) + q * SPW + lane / NP;
         const double pr = P_at[u][q] * P_bt[u][q];
-        const double z = group_sum<NP>(pr);
+        const double z = lanes_sum<NP>(pr);
         const double rz = z != 0.0 ? 1.0 / z : 0.0;
         Ab[jj][y] = P_ap[u][q];
         Gb[jj][y] = P_bt[u][q] * P_e[u][q] * __builtin_ldexp(rz, P_sc[u][q]);
@@ -1159,7 +1039,7 @@ __global__ __launch_bounds__(kXwThreads) __attribute__((amdgpu_waves_per_eu(XiCf
       for (int k = 0; k < K; k++)
         u = __builtin_fma(Tc[lane * K + k], (o0 && a.nleaf ? op_leaf_e(a, o0, k) : 1.0) * bz[k], u);
     const double pr = xs ? a.pi[lane] * u : 0.0;
-    const double z = group_sum<64>(pr);
+    const double z = lanes_sum<64>(pr);
     p0s[s][lane] = z != 0.0 ? pr / z : pr;
   }
   __syncthreads();

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "model.h"
+#include "wave_ops.h"
 
 namespace nipamd {
 
@@ -45,35 +46,6 @@ struct FoldArgs {
   int lds;                // the block's table slice is staged in LDS
   double* out;            // [G][64][64]
 };
-
-template <int K>
-__device__ __forceinline__ double ror(double v) {     // row_ror:K of a double
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x120 + K, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x120 + K, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-// sum over the wave in a fixed order (every lane ends with the same bits)
-__device__ __forceinline__ double wave_sum(double x) {
-  asm("" : "+v"(x));       // one rounded value per lane: no fma contraction into the first add
-  x += ror<8>(x);
-  x += ror<4>(x);
-  x += ror<2>(x);
-  x += ror<1>(x);
-  {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    x = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-  }
-  {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    x = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-  }
-  return x;
-}
 
 __global__ __launch_bounds__(kFoldWaves * 64, 1)
 void fold_kernel(FoldArgs f) {
@@ -114,7 +86,7 @@ void fold_kernel(FoldArgs f) {
     const double t = base[off[h]] * w[h];
     if (r == 0) a0 += t; else if (r == 1) a1 += t; else a2 += t;
   }
-  const double s = wave_sum((a0 + a1) + (a2 + a3));
+  const double s = lanes_sum<64>((a0 + a1) + (a2 + a3));
   if (lane == 0) f.out[((size_t)g * 64 + x) * 64 + y] = s;
 }
 

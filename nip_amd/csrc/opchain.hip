@@ -24,6 +24,7 @@
 #include "chain_kernels.h"
 #include "opchain.h"
 #include "diag.h"
+#include "dpp_row.h"
 
 namespace nipamd {
 namespace {
@@ -31,47 +32,6 @@ namespace {
 constexpr int kOpSeqs = 8;
 constexpr int kOpThreads = 256;
 constexpr int kOpGuard = 1;
-
-template <int K>
-__device__ __forceinline__ double ror(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const int rl = __builtin_amdgcn_mov_dpp(lo, 0x120 + K, 0xF, 0xF, true);
-  const int rh = __builtin_amdgcn_mov_dpp(hi, 0x120 + K, 0xF, 0xF, true);
-  return __hiloint2double(rh, rl);
-}
-
-__device__ __forceinline__ double rsum(double x) {
-  asm("" : "+v"(x));                       // one rounded value per lane (no fma contraction)
-  x += ror<8>(x);
-  x += ror<4>(x);
-  x += ror<2>(x);
-  x += ror<1>(x);
-  return x;
-}
-
-template <int J, bool NOP>
-__device__ __forceinline__ void fbc(double& acc, double v, double c) {
-  if (NOP)
-    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc) : "v"(v), "v"(c), "n"(J));
-  else
-    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc) : "v"(v), "v"(c), "n"(J));
-}
-
-// sum_k x[lane k] * c[k] over the row (c[k] = 0 for k >= K)
-__device__ __forceinline__ double dot16(double x, const double (&c)[16]) {
-  double a0 = 0.0, a1 = 0.0;
-  fbc<0, true>(a0, x, c[0]);   fbc<1, false>(a1, x, c[1]);
-  fbc<2, false>(a0, x, c[2]);  fbc<3, false>(a1, x, c[3]);
-  fbc<4, false>(a0, x, c[4]);  fbc<5, false>(a1, x, c[5]);
-  fbc<6, false>(a0, x, c[6]);  fbc<7, false>(a1, x, c[7]);
-  fbc<8, false>(a0, x, c[8]);  fbc<9, false>(a1, x, c[9]);
-  fbc<10, false>(a0, x, c[10]); fbc<11, false>(a1, x, c[11]);
-  fbc<12, false>(a0, x, c[12]); fbc<13, false>(a1, x, c[13]);
-  fbc<14, false>(a0, x, c[14]); fbc<15, false>(a1, x, c[15]);
-  return a0 + a1;
-}
 
 __device__ __forceinline__ double div_or_keep(double x, double c) { return c != 0.0 ? x / c : x; }
 
@@ -183,9 +143,9 @@ void op_fb_kernel(OpArgs a) {
 #pragma unroll
     for (int k = 0; k < 16; k++) C[k] = Cn[k];
     coef(code_at(tnext), Cn);
-    const double m1v = rsum(x * wy);
-    const double u = __builtin_ldexp(dot16(x, C), sc);
-    const double z = rsum(u);
+    const double m1v = row_sum(x * wy);
+    const double u = __builtin_ldexp(dot2_bcast(x, C), sc);
+    const double z = row_sum(u);
     if (fwd && valid && c != 0) {                       // a forward step with evidence
       m2 *= z;
       m1 *= __builtin_ldexp(m1v, sc);
@@ -206,7 +166,7 @@ void op_fb_kernel(OpArgs a) {
     } else {
       const double o = Srow[(long)tc * 16];
       const double pr = u * o;
-      const double z = rsum(pr);
+      const double z = row_sum(pr);
       if (est) {
         // the step's xi weights: sum_y u o = 2^sc Z' (Z' the xi mass at the
         // messages' own scale); forward rows W_t = alpha^_{t-1} (x) beta^_t,
@@ -255,10 +215,10 @@ void op_fb_kernel(OpArgs a) {
       // t = 0 when H = 0)
       double C0[16];
       coef(cd[0], C0);
-      const double u0 = __builtin_ldexp(dot16(x, C0), sc);
+      const double u0 = __builtin_ldexp(dot2_bcast(x, C0), sc);
       const double piy = ys ? a.pi[y] : 0.0;
       const double pr = piy * u0;
-      const double z = rsum(pr);
+      const double z = row_sum(pr);
       if (active && ys) a.P0[(size_t)b * K + y] = div_or_keep(pr, z);
       const double f = z != 0.0 ? __builtin_ldexp(1.0 / z, sc) : 0.0;
       xi_row(piy, x * f, a.W + (size_t)b * T * KK, K, y, H > 0 && active && ys);
