@@ -8,30 +8,48 @@
 // messages from two of them -- each checkpoint is one of the chunk's rows and
 // seeds a 3-step chain for the other three of its half (two independent
 // chains, interleaved) -- on the partner SIMDs, one chunk at a time, in step
-// with the filter that consumes them:
+// with the filter that consumes them.
 //
-//   SIMD 0: wave 0 forward filter (alpha, rings, z2)        wave 4 backward posteriors,
-//                                                                    chains 8-15
-//   SIMD 1: wave 1 backward filter (beta)                    wave 5 forward posteriors,
-//                                                                    chains 8-15
-//   SIMD 2: wave 2 forward partner (ll; alpha checkpoints    wave 6 recomputes
-//           in phase A; posteriors t >= H, chains 0-7)               beta of t >= H
-//   SIMD 3: wave 3 backward partner (beta checkpoints         wave 7 recomputes
-//           in phase A; posteriors t < H, chains 0-7)                alpha of t < H
+// The two phases use different step forms.  Phase A is latency: two chained
+// matrix-core filters per CU would leave the f64 VALU of all four SIMDs idle,
+// so there all eight waves are row-form filters (RowsA: a 16-lane DPP row per
+// sequence, half the step latency for 1.75x the pipe time), four chains each,
+// and there is no barrier at all.  Phase B is pipe time: the matrix-core
+// filters, with the roles below.  At the phase barrier the row waves hand the
+// filters' next input, the pending scale and the forward ll to phase B through
+// LDS (kHand*, chain_mfma_core.h).
+//
+//           phase A (rows)        phase B
+//   SIMD 0: wave 0 forward 0-3    forward filter (alpha, rings, z2)
+//           wave 4 backward 0-3   backward posteriors, chains 8-15
+//   SIMD 1: wave 1 forward 4-7    backward filter (beta)
+//           wave 5 backward 4-7   forward posteriors, chains 8-15
+//   SIMD 2: wave 2 forward 8-11   forward partner (ll; posteriors t >= H, chains 0-7)
+//           wave 6 backward 8-11  recomputes beta of t >= H
+//   SIMD 3: wave 3 forward 12-15  backward partner (posteriors t < H, chains 0-7)
+//           wave 7 backward 12-15 recomputes alpha of t < H
 //
 // (a workgroup's waves go to the CU's SIMDs round robin: wave w on SIMD w % 4).
-// The filters keep their SIMD's double-precision pipe to themselves; the
-// recompute wave's matrix-core chain shares a SIMD with the partner's in-lane
-// normalisation and stores.  HBM per sequence-step: the observation (4 B),
-// the posterior (128 B), checkpoints (2 x 32 B: written once, read once).
+// In phase B the filters keep their SIMD's double-precision pipe to
+// themselves; the recompute wave's matrix-core chain shares a SIMD with the
+// partner's in-lane normalisation and stores.  HBM per sequence-step: the
+// observation (4 B), the posterior (128 B), checkpoints (2 x 32 B: written
+// once, read once).
 //
 // Phase B rescales sparsely, like phase A (the forward partner sums alpha
 // itself for the ll).  Results agree with chain_fb_mfma_kernel's to the last
 // bits (tests/test_gpu_ckpt.py) and with the oracle within DESIGN.md's
-// tolerances.
+// tolerances.  Diagnostics builds keep the matrix-core phase A (the filters
+// of phase B from t = 0 and T - 2, the partners draining their rings into
+// checkpoints and ll, a barrier per chunk) behind NIPAMD_CK_PHASEA=mfma
+// (tests/test_gpu_ckpt_rows.py compares the two).
 // The same recursion as nip.c:1320-1581 (forward_backward_inference), see
 // chain_kernels.hip for the derivation.
+#include <cstring>
+
 #include "chain_mfma_core.h"
+#include "diag.h"
+#include "dpp_row.h"
 #include "store_pol.h"
 
 namespace nipamd {
@@ -57,7 +75,10 @@ __device__ __forceinline__ int ck_off(int k, int j, int p) {
 
 // diagnostics builds (NIPAMD_WAIT_TIMES): per-wave cycle stamps, a.diag[block][wave][5] =
 // phase A, phase-barrier wait, phase B, phase-B barrier waits, SIMD id (HW_ID[5:4])
+// (rows: every wave's phase A is its row-form filter; the recompute waves
+// keep their steps cycles in slot 1)
 struct CkDiag {
+  bool rows = false;
   unsigned long long t0 = 0, ta = 0, tb = 0;
   unsigned long long x1 = 0, x2 = 0, tx = 0;   // recompute waves: chunk set-up / steps cycles
   bool rc = false;
@@ -74,8 +95,208 @@ struct CkDiag {
   __device__ __forceinline__ void write(const ChainArgs& a, int wave, int lane) {
     if (!NIPAMD_WAIT_TIMES || !a.diag || lane != 0) return;
     unsigned long long* d = a.diag + (size_t)blockIdx.x * 40 + wave * 5;
-    d[0] = rc ? x1 : ta - t0; d[1] = rc ? x2 : tb - ta; d[2] = __builtin_readcyclecounter() - tb; d[3] = wb.cyc;
+    d[0] = (rc && !rows) ? x1 : ta - t0; d[1] = rc ? x2 : tb - ta; d[2] = __builtin_readcyclecounter() - tb; d[3] = wb.cyc;
     d[4] = (__builtin_amdgcn_s_getreg(4 | (31 << 11)) >> 4) & 3;   // hwreg(HW_REG_HW_ID)
+  }
+};
+
+// Phase A in row form.  Wave q of a direction owns the chains 4q..4q+3, one
+// per 16-lane DPP row (lane s holds state s; the mat-vec is dot2_bcast's 16
+// v_fmac_f64_dpp row_newbcast).  A wave does everything for its chains from
+// the LDS codes and evidence table -- evidence, power-of-two rescaling, the
+// checkpoint rows (rescaled, stored straight from registers into Sblk) and,
+// forward, the ll factors of LL::step -- so phase A has no barrier.
+// Steps are grouped by four so that every group starts on a checkpoint step
+// (forward (H - t) & 3 == 0, backward (t - H) & 3 == 3: the steps the
+// recompute waves start from); the n & 3 steps before the first group rescale
+// every step, a group rescales on its first step (forward: with the
+// checkpoint's exponent) or its last (backward), and the phase's last step
+// always does, so the matrix-core filter starts phase B from a scaled vector.
+//
+// Two waves share a SIMD and the VALU issues one instruction per four cycles
+// whatever its width, so phase A's time is the instruction count of a forward
+// plus a backward step (profiles/ckpt_rows/README.md).  Hence:
+//  - the rescale exponent is that of the row's largest element, from the
+//    integer maximum of the doubles' high words (non-negative doubles order
+//    like their bit patterns): one DPP max per tree level where an f64 sum
+//    costs three instructions per level.  Any power of two serves: the ll
+//    carries the exponents that were applied, posteriors are scale-free;
+//  - the forward ll (a step needs z2 = sum(alpha_t) and y = alpha_t . w) is
+//    taken a group at a time through LDS: each step leaves alpha_t in the
+//    wave's block, after the group lane (r, j) reads the quarter j & 3 of
+//    step j >> 2 of chain r back (four states, one 32-byte read), sums it in
+//    lane, and two quad levels finish z2 (even lanes) and y (odd lanes) of
+//    four steps at once.  A lane keeps the product of its own steps' factors,
+//    mantissa and exponent apart as LL does; the row's four quads are
+//    multiplied at the hand-over.  The reads of one group are consumed after
+//    the next group's steps, so no step waits for them.
+template <bool FWD>
+struct RowsA {
+  double Acol[16];          // forward: column s of A (alpha' = A^T alpha); backward: row s
+  double X;                 // next mat-vec input (fwd: alpha_{t-1}; bwd: e_{t+1} o beta_{t+1})
+  int sc;                   // power-of-two scale of the next mat-vec result
+  double e_cur;             // evidence factor of the next step, its successor's code
+  int c_nx;
+  const uint8_t* cd;        // LDS codes of this row's chain, index t
+  const double* Es;         // LDS evidence table + s
+  double* Sc;               // checkpoint rows of this chain, state s: Sblk + ch * 16 + s
+  // forward ll
+  double* Lw;               // this lane's slot of a step in the wave's LDS block [4 steps][64 lanes]
+  const double* Lr;         // the four states this lane reads back
+  double wq[4];             // w of those states
+  double2 v01, v23;         // read back, not yet consumed
+  double m, zmin;           // even lanes: m2's mantissa product and the smallest z2; odd lanes: m1's
+  int ex, scsum;            // the product's exponent; the sum of the scales applied (m1's 2^sc)
+  bool odd;
+
+  // -(frexp exponent) of the row's largest element; for an all-zero row any value serves
+  __device__ __forceinline__ static int row_scale(double p) {
+    int h = __double2hiint(p);
+    h = max(h, __builtin_amdgcn_mov_dpp(h, 0x128, 0xF, 0xF, true));   // row_ror:8
+    h = max(h, __builtin_amdgcn_mov_dpp(h, 0x124, 0xF, 0xF, true));   // row_ror:4
+    h = max(h, __builtin_amdgcn_mov_dpp(h, 0x122, 0xF, 0xF, true));   // row_ror:2
+    h = max(h, __builtin_amdgcn_mov_dpp(h, 0x121, 0xF, 0xF, true));   // row_ror:1
+    return 1022 - (h >> 20);
+  }
+  // one step: u = the scaled mat-vec result, returns p = u o e (the next input)
+  __device__ __forceinline__ double matvec_e(double& u) {
+    constexpr int dir = FWD ? 1 : -1;
+    const double e = e_cur;
+    e_cur = Es[c_nx * kEtStride];                 // one step ahead; its code two steps ahead
+    c_nx = cd[2 * dir];                           // (the guards cover the over-run)
+    cd += dir;
+    u = __builtin_ldexp(dot2_bcast(X, Acol), sc);
+    const double p = u * e;
+    X = p;
+    return p;
+  }
+  // forward step t, the k-th of its group: RS rescale, CK checkpoint (then RS too)
+  template <bool RS, bool CK>
+  __device__ __forceinline__ void fstep(int t, int k) {
+    double u;
+    const double p = matvec_e(u);
+    Lw[k * 64] = p;
+    if (RS || CK) {
+      sc = row_scale(p);
+      scsum += sc;                                // m1_{t+1} = 2^sc y_t
+      if (CK) store_pol<NIPAMD_SCR_NT>(Sc + (long)t * kSStep, __builtin_ldexp(p, sc));
+    } else {
+      sc = 0;
+    }
+  }
+  // backward step t
+  template <bool RS, bool CK>
+  __device__ __forceinline__ void bstep(int t) {
+    double u;
+    const double p = matvec_e(u);
+    if (CK) store_pol<NIPAMD_SCR_NT>(Sc + (long)t * kSStep, __builtin_ldexp(u, row_scale(u)));
+    sc = RS ? row_scale(p) : 0;
+  }
+  __device__ __forceinline__ void ll_read() {
+    v01 = *reinterpret_cast<const double2*>(Lr);
+    v23 = *reinterpret_cast<const double2*>(Lr + 2);
+  }
+  // the factors of the step this lane read back (valid: the block held that step)
+  __device__ __forceinline__ void ll_take(bool valid) {
+    double z = (v01.x + v01.y) + (v23.x + v23.y);
+    double y = __builtin_fma(v23.y, wq[3], __builtin_fma(v23.x, wq[2], __builtin_fma(v01.y, wq[1], v01.x * wq[0])));
+    asm("" : "+v"(z), "+v"(y));                   // one rounded value each: no contraction into the adds below
+    z += dpp64<0xB1>(z);                          // quad_perm [1,0,3,2]
+    y += dpp64<0xB1>(y);
+    double v = odd ? y : z;
+    v += dpp64<0x4E>(v);                          // quad_perm [2,3,0,1]: even lanes z2_t, odd lanes y_t
+    v = valid ? v : 1.0;
+    zmin = __builtin_fmin(zmin, v);               // (the even lanes' is the chain's)
+    m *= __builtin_amdgcn_frexp_mant(v);
+    ex += __builtin_amdgcn_frexp_exp(v);
+  }
+  __device__ __forceinline__ void renorm() {
+    const int k = __builtin_amdgcn_frexp_exp(m);
+    m = __builtin_ldexp(m, -k);
+    ex += k;
+  }
+
+  // hand: this direction's hand-over block (chain_mfma_core.h); lbuf: the
+  // wave's 2 KB LDS block (forward)
+  __device__ __forceinline__ void run(const ChainArgs& a, const double* Et, const uint8_t* codes, int Tr,
+                                      double* Sblk, double* hand, double* lbuf, int q, int lane) {
+    const int r = lane >> 4, s = lane & 15, ch = 4 * q + r;
+    const int T = a.T, H = a.H;
+    const int n = FWD ? H : T - 1 - H;            // forward alpha_0..alpha_{H-1}; backward beta_{T-2}..beta_H
+    const int t0 = FWD ? 0 : T - 2;
+    constexpr int dir = FWD ? 1 : -1;
+#pragma unroll
+    for (int i = 0; i < 16; i++) Acol[i] = FWD ? a.A[i * 16 + s] : a.A[s * 16 + i];
+    Es = Et + s;
+    Sc = Sblk + ch * 16 + s;
+    cd = codes + ch * Tr + kMG + t0;
+    sc = 0;
+    if (FWD) {
+      X = a.pi[s];
+      double ym = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; i++) ym = __builtin_fma(a.pi[i], a.ts[i], ym);   // y_{-1} (LL::init)
+      Lw = lbuf + lane;
+      Lr = lbuf + (s >> 2) * 64 + r * 16 + 4 * (s & 3);
+#pragma unroll
+      for (int i = 0; i < 4; i++) wq[i] = a.ts[4 * (s & 3) + i];
+      odd = (s & 1) != 0;
+      m = s == 1 ? ym : 1.0; zmin = 1.0; ex = 0; scsum = 0;
+    } else {
+      const double beta = s < a.N ? 1.0 : 0.0;    // beta_{T-1} = 1 on the real states
+      Sc[(long)(T - 1) * kSStep] = beta;          // the beta recompute's top row
+      X = Es[cd[1] * kEtStride] * beta;
+      sc = row_scale(X);
+    }
+    e_cur = Es[cd[0] * kEtStride];
+    c_nx = cd[dir];
+    int t = t0, i = 0;
+    const int pre = n & 3;
+    for (; i < pre; i++, t += dir) {
+      if (FWD) fstep<true, false>(t, i);
+      else bstep<true, false>(t);
+    }
+    if (FWD && pre > 0) {
+      ll_read();
+      ll_take((s >> 2) < pre);
+    }
+    bool pending = false;
+    for (; i < n; i += 4, t += 4 * dir) {
+      const bool last = i + 4 >= n;
+      if (FWD) {
+        fstep<true, true>(t, 0);
+        fstep<false, false>(t + 1, 1);
+        fstep<false, false>(t + 2, 2);
+        if (last) fstep<true, false>(t + 3, 3);
+        else fstep<false, false>(t + 3, 3);
+        if (pending) ll_take(true);               // the previous group's
+        if ((i & 63) < 4) renorm();
+        ll_read();
+        pending = true;
+      } else {
+        bstep<false, true>(t);
+        bstep<false, false>(t - 1);
+        bstep<false, false>(t - 2);
+        bstep<true, false>(t - 3);
+      }
+    }
+    hand[ch * 16 + s] = X;
+    if (s == 0) reinterpret_cast<int*>(hand + kHandSc)[ch] = sc;
+    if (FWD) {
+      if (pending) ll_take(true);
+      // the row's four quads hold a step each of every group: multiply them
+      renorm();
+      m *= row_ror<8>(m);
+      m *= row_ror<4>(m);
+      ex += __builtin_amdgcn_mov_dpp(ex, 0x128, 0xF, 0xF, true);
+      ex += __builtin_amdgcn_mov_dpp(ex, 0x124, 0xF, 0xF, true);
+      zmin = __builtin_fmin(zmin, row_ror<8>(zmin));
+      zmin = __builtin_fmin(zmin, row_ror<4>(zmin));
+      renorm();
+      double* L = hand + kHandLL + ch * 5;
+      if (s == 0) { L[0] = m; L[2] = (double)ex; L[4] = zmin; }
+      if (s == 1) { L[1] = m; L[3] = (double)(ex + scsum); }
+    }
   }
 };
 
@@ -94,7 +315,9 @@ struct CkDiag {
 // and runs at most three steps without rescaling (phase A's sparse rescaling
 // relies on four); the posterior normalisation removes the scale.  The next
 // chunk's evidence vectors and the checkpoints two chunks ahead are loaded
-// while a chunk runs.
+// while a chunk runs.  (Sum ~1 is the matrix-core phase A's checkpoint, the
+// diagnostics path; RowsA scales a checkpoint by its largest element, so its
+// sum lies in [0.5, 16): the three steps and norm_store take either.)
 template <bool FWD>
 __device__ __forceinline__ void recompute_wave(const ChainArgs& a, const WaveCtx& c, const double* Sw, int lane,
                                                int nchA, int nchB, CkDiag& dg) {
@@ -324,7 +547,8 @@ __device__ __forceinline__ void norm_store(const ChainArgs& a, const double* fsl
 
 template <bool FWD, int PROJ>
 __device__ __forceinline__ void ck_partner(const ChainArgs& a, double* out, double* rring, const double* zr,
-                                           double* Sblk, int lane, long b0, int nchA, int nchB, CkDiag& dg) {
+                                           double* Sblk, int lane, long b0, int nchA, int nchB, CkDiag& dg,
+                                           const double* hand) {
   const int T = a.T, H = a.H;
   const int s = lane & 7, hi = lane >> 3;
   const int c = lane & 15, kq = lane >> 4;
@@ -333,7 +557,10 @@ __device__ __forceinline__ void ck_partner(const ChainArgs& a, double* out, doub
   constexpr int dir = FWD ? 1 : -1;
 
   LL ll;
-  if (FWD) ll.init(a, lane, false);
+  if (FWD) {
+    ll.init(a, lane, false);
+    if (hand) ll.m1 = 1.0;                           // row-form phase A: y_{-1} is in the hand-over's m1
+  }
   auto ring_vec = [&](const double* slot, int k, double (&v)[16]) {
 #pragma unroll
     for (int p = 0; p < 8; p++) {
@@ -341,7 +568,8 @@ __device__ __forceinline__ void ck_partner(const ChainArgs& a, double* out, doub
       v[2 * p] = x.x; v[2 * p + 1] = x.y;
     }
   };
-  // phase A: the forward ll (as chain_mfma.hip's partner) and the checkpoints
+  // matrix-core phase A only (diagnostics builds, nchA > 0; with RowsA the rows
+  // keep both): the forward ll (as chain_mfma.hip's partner) and the checkpoints
   auto drainA = [&](int ci) {
     const double* slot = out + (ci & 1) * kSlotD;
     if (FWD) {
@@ -392,6 +620,10 @@ __device__ __forceinline__ void ck_partner(const ChainArgs& a, double* out, doub
   dg.stamp(dg.ta);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // phase barrier
   dg.stamp(dg.tb);
+  if (FWD && hand && kq == 0) {                      // the forward rows' ll so far, on the chain's first lane
+    const double* L = hand + kHandLL + c * 5;
+    ll.m2 = L[0]; ll.m1 = L[1]; ll.e2 = (int)L[2]; ll.e1 = (int)L[3]; ll.zmin = L[4];
+  }
 
   double* const sink = a.S + (size_t)((a.B + kMSeq - 1) / kMSeq) * block_scratch(T) + 2 * s;
   // phase B: the forward ll from the filter's ring (phase B rescales like
@@ -420,7 +652,11 @@ __device__ __forceinline__ void ck_partner(const ChainArgs& a, double* out, doub
   barrier_lds();                                     // the block's closing barrier
 }
 
-template <int PROJ>
+// ROWS: phase A in row form on all eight waves (RowsA), handed over to the
+// matrix-core phase B through LDS; !ROWS (diagnostics builds,
+// NIPAMD_CK_PHASEA=mfma): the matrix-core phase A of the filter waves with the
+// partners' checkpoints and ll, a chunk barrier per eight steps.
+template <int PROJ, bool ROWS>
 #ifndef NIPAMD_CK_PRIO
 // 5: the filters at s_setprio 2, the recompute waves at 1, the partners at 0:
 // -1.2% against 3 in 10 of 12 interleaved pairs (profiles/r05/gpu/r05af_ab_fb_prio.txt,
@@ -448,13 +684,32 @@ __global__ __launch_bounds__(kCThreads, 1) void chain_fb_ckpt_kernel(ChainArgs a
   stage_codes<kCThreads, decltype(nozero), kEtStride>(a, b0, tid, Et, codes, Tr, nozero);
   __syncthreads();
   CkDiag dg;
+  dg.rows = ROWS;
   dg.stamp(dg.t0);
 
   const int H = a.H;
   const int nA = (H > T - 1 - H ? H : T - 1 - H);
   const int nB = (T - H > H ? T - H : H);
-  const int nchA = (nA + kMChunk - 1) / kMChunk, nchB = (nB + kMChunk - 1) / kMChunk;
+  // chunk barriers of phase A: none in row form.  Every wave then passes the
+  // phase barrier, nchB chunk barriers and the closing barrier, whatever T and
+  // however many of the block's sequences exist (absent ones run as missing).
+  const int nchA = ROWS ? 0 : (nA + kMChunk - 1) / kMChunk, nchB = (nB + kMChunk - 1) / kMChunk;
   double* Sblk = a.S + (size_t)blockIdx.x * block_scratch(T) + kMG * kSStep;   // t = 0
+  // hand-over blocks (chain_mfma_core.h): slot 1 of each direction's filter
+  // ring, idle until that filter's chunk 1 -- by then (chunk 0's barrier) the
+  // filter and the forward partner have read them
+  double* const hf = ROWS ? out + kSlotD : nullptr;
+  double* const hb = ROWS ? out + 3 * kSlotD : nullptr;
+  static_assert(kHandD <= kSlotD, "hand-over block");
+  if (ROWS) {
+    if (wave < 4) {
+      RowsA<true> ra;
+      ra.run(a, Et, codes, Tr, Sblk, hf, rr + wave * 256, wave, lane);   // rr: idle until phase B
+    } else {
+      RowsA<false> ra;
+      ra.run(a, Et, codes, Tr, Sblk, hb, nullptr, wave - 4, lane);
+    }
+  }
   const int role = wave & 3;
   const bool fwd = (wave & 1) == 0;
   double* ring = out + (fwd ? 0 : 2 * kSlotD);      // the filter's ring of this side
@@ -489,8 +744,8 @@ __global__ __launch_bounds__(kCThreads, 1) void chain_fb_ckpt_kernel(ChainArgs a
   if ((NIPAMD_CK_PRIO == 4 || NIPAMD_CK_PRIO == 5) && wave >= 6) __builtin_amdgcn_s_setprio(1);
   if (NIPAMD_CK_PRIO == 6 && wave >= 6) __builtin_amdgcn_s_setprio(2);
   if (role >= 2 && wave < 4) {
-    if (fwd) ck_partner<true, PROJ>(a, ring, rring, zr, Sblk, lane, b0, nchA, nchB, dg);
-    else ck_partner<false, PROJ>(a, ring, rring, zr, Sblk, lane, b0, nchA, nchB, dg);
+    if (fwd) ck_partner<true, PROJ>(a, ring, rring, zr, Sblk, lane, b0, nchA, nchB, dg, hf);
+    else ck_partner<false, PROJ>(a, ring, rring, zr, Sblk, lane, b0, nchA, nchB, dg, hb);
     dg.write(a, wave, lane);
     return;
   }
@@ -515,13 +770,18 @@ __global__ __launch_bounds__(kCThreads, 1) void chain_fb_ckpt_kernel(ChainArgs a
   }
   c.out = ring;
   c.zw = g == 0;
-  if (fwd) filter_wave<true, false, true, 1>(a, c, Et, Sw, lane, true, b0 + j, nchA, nchB, nullptr);
-  else filter_wave<false, false, true, 1>(a, c, Et, Sw, lane, true, b0 + j, nchA, nchB, nullptr);
+  if (ROWS) dg.stamp(dg.ta);                         // the filters: phase A (rows); the rest in slot 2
+  if (fwd) filter_wave<true, false, true, 1>(a, c, Et, Sw, lane, true, b0 + j, nchA, nchB, nullptr, hf, &dg.wb);
+  else filter_wave<false, false, true, 1>(a, c, Et, Sw, lane, true, b0 + j, nchA, nchB, nullptr, hb, &dg.wb);
   barrier_lds();
-  dg.tb = dg.ta = dg.t0;                             // the filters: total only (slot 2)
-  dg.x2 = dg.t0 - t_entry;                           // and the prologue (staging) in slot 1
-  dg.rc = true;
-  dg.x1 = 0;
+  if (ROWS) {
+    dg.tb = dg.ta;
+  } else {
+    dg.tb = dg.ta = dg.t0;                           // matrix-core phase A: total only (slot 2)
+    dg.x2 = dg.t0 - t_entry;                         // and the prologue (staging) in slot 1
+    dg.rc = true;
+    dg.x1 = 0;
+  }
   dg.write(a, wave, lane);
 }
 
@@ -531,6 +791,28 @@ size_t chain_fb_ckpt_lds_bytes(int M, int T) {
   return (size_t)(2 * kOutD + kZD) * sizeof(double) + (size_t)(M + 2) * kEtStride * sizeof(double) +
          (size_t)kMSeq * chain_codes_row(T);
 }
+
+namespace {
+template <int PROJ, bool ROWS>
+int launch_ckpt_as(const ChainArgs& a, size_t lds, int blocks, hipStream_t stream) {
+  static size_t lds_set[kMaxDevices] = {};
+  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_fb_ckpt_kernel<PROJ, ROWS>), lds, lds_set)) return rc;
+  hipLaunchKernelGGL((chain_fb_ckpt_kernel<PROJ, ROWS>), dim3(blocks), dim3(kCThreads), lds, stream, a);
+  return 0;
+}
+// diagnostics builds: NIPAMD_CK_PHASEA=mfma selects the matrix-core phase A
+template <int PROJ>
+int launch_ckpt(const ChainArgs& a, size_t lds, int blocks, hipStream_t stream) {
+#ifdef NIPAMD_DIAGNOSTICS
+  static const bool mfmaA = [] {
+    const char* e = diag_env("NIPAMD_CK_PHASEA");
+    return e && std::strcmp(e, "mfma") == 0;
+  }();
+  if (mfmaA) return launch_ckpt_as<PROJ, false>(a, lds, blocks, stream);
+#endif
+  return launch_ckpt_as<PROJ, true>(a, lds, blocks, stream);
+}
+}  // namespace
 
 int chain_fb_ckpt_launch(const ChainArgs& a, hipStream_t stream) {
   const size_t lds = (chain_fb_ckpt_lds_bytes(a.M, a.T) + 15) & ~(size_t)15;
@@ -543,24 +825,12 @@ int chain_fb_ckpt_launch(const ChainArgs& a, hipStream_t stream) {
   if (proj) {
     int cmax = 0;
     for (int jv = 0; jv < a.nproj; jv++) cmax = a.proj_card[jv] > cmax ? a.proj_card[jv] : cmax;
-    if (cmax <= 4) {
-      static size_t s4[kMaxDevices] = {};
-      if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_fb_ckpt_kernel<4>), lds, s4)) return rc;
-      hipLaunchKernelGGL(chain_fb_ckpt_kernel<4>, dim3(blocks), dim3(kCThreads), lds, stream, a);
-    } else if (cmax <= 8) {
-      static size_t s8[kMaxDevices] = {};
-      if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_fb_ckpt_kernel<8>), lds, s8)) return rc;
-      hipLaunchKernelGGL(chain_fb_ckpt_kernel<8>, dim3(blocks), dim3(kCThreads), lds, stream, a);
-    } else {
-      static size_t s16[kMaxDevices] = {};
-      if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_fb_ckpt_kernel<16>), lds, s16)) return rc;
-      hipLaunchKernelGGL(chain_fb_ckpt_kernel<16>, dim3(blocks), dim3(kCThreads), lds, stream, a);
-    }
+    const int rc = cmax <= 4 ? launch_ckpt<4>(a, lds, blocks, stream)
+                 : cmax <= 8 ? launch_ckpt<8>(a, lds, blocks, stream) : launch_ckpt<16>(a, lds, blocks, stream);
+    if (rc) return rc;
     g_last_kernel = "chain_fb_ckpt_kernel<proj>";
   } else {
-    static size_t lds_set[kMaxDevices] = {};
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&chain_fb_ckpt_kernel<0>), lds, lds_set)) return rc;
-    hipLaunchKernelGGL(chain_fb_ckpt_kernel<0>, dim3(blocks), dim3(kCThreads), lds, stream, a);
+    if (int rc = launch_ckpt<0>(a, lds, blocks, stream)) return rc;
     g_last_kernel = "chain_fb_ckpt_kernel";
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;

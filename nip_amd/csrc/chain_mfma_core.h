@@ -221,10 +221,22 @@ struct Chain {
   }
 };
 
+// LDS hand-over from row-form phase-A waves (chain_ckpt.hip) to the phase-B
+// waves, one block per direction: the filter's next input X in natural state
+// order [chain][16], the pending scale exponents [chain], and (forward) the ll
+// state of each chain {m2, m1, e2, e1, zmin}
+constexpr int kHandSc = kMSeq * 16;                // ints, at double offset 256
+constexpr int kHandLL = kHandSc + kMSeq / 2;       // doubles [chain][5]
+constexpr int kHandD = kHandLL + kMSeq * 5;
+
+// hand (chain_ckpt.hip, with nchA = 0): phase A ran elsewhere; the filter
+// takes its phase-B input and pending scale from the hand-over block after
+// the phase barrier
 template <bool FWD, bool ES = false, bool SPARSE_B = false, int SW = 0>
 __device__ __forceinline__ void filter_wave(const ChainArgs& a, const WaveCtx& c, const double* Et,
                                             double* Sw, int lane, bool active, long b,
-                                            int nchA, int nchB, unsigned long long* stamps) {
+                                            int nchA, int nchB, unsigned long long* stamps,
+                                            const double* hand = nullptr, WaitAcc* wbd = nullptr) {
   const int j = lane & 15, g = lane >> 4;
   const int sj = state_of(j & 3, j >> 2);       // actual state of D row j
   const int T = a.T, H = a.H;
@@ -232,7 +244,9 @@ __device__ __forceinline__ void filter_wave(const ChainArgs& a, const WaveCtx& c
 #pragma unroll
   for (int r = 0; r < 4; r++)
     ch.Aop[r] = FWD ? a.A[state_of(g, r) * 16 + sj] : a.A[sj * 16 + state_of(g, r)];
-  if (FWD) {
+  if (hand) {
+    ch.X = v4d{0.0, 0.0, 0.0, 0.0};             // phase A ran elsewhere: X, sc (and S[T-1]) come from there
+  } else if (FWD) {
     ch.X = load4(a.pi + 2 * g);
     if (ES) {                                   // S[-1] = alpha_{-1} = prior: the backward partner's P0 step
       double* q = Sw - kSStep;
@@ -259,11 +273,16 @@ __device__ __forceinline__ void filter_wave(const ChainArgs& a, const WaveCtx& c
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // phase barrier
   if (stamps && lane == 0) stamps[blockIdx.x * 4 + 2] = __builtin_readcyclecounter();
   if (ES && FWD) diag_stamp(a, 2, lane);
+  if (hand) {
+    ch.X = load4(hand + j * 16 + 2 * g);
+    ch.sc = reinterpret_cast<const int*>(hand + kHandSc)[j];
+  }
   // phase B: forward alpha_H..alpha_{T-1}; backward beta_{H-1}..beta_0 (e_step:
   // ..beta_{-1}, the step against alpha_{-1} = prior that yields P0 and xi_0)
   // (SPARSE_B: phase B rescales like phase A; the partner then sums alpha itself)
   if (FWD) ch.template run<SPARSE_B>(c, T - H, nchB, H, lane, &wb);
   else ch.template run<SPARSE_B>(c, ES ? H + 1 : H, nchB, H - 1, lane, &wb);
+  if (NIPAMD_WAIT_TIMES && wbd) wbd->cyc = wb.cyc;
   if (NIPAMD_WAIT_TIMES && a.counts && lane == 0) {
     unsigned long long* st = reinterpret_cast<unsigned long long*>(a.counts) + (size_t)gridDim.x * 4;
     st[blockIdx.x * 8 + (FWD ? 0 : 1)] = wa.cyc;

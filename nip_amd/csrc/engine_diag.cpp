@@ -79,10 +79,16 @@ void report_ckpt_waves(const Stamps& w, int nblk) {
   if (!(m[2] > 0)) return;
   std::fprintf(stderr, "[nipamd] ckpt kernel cycles per wave (phase A / phase-barrier wait / phase B / "
                "phase-B barrier waits / mean SIMD id; block 0's SIMD ids):\n");
-  static const char* names[8] = {"fwd filter", "bwd filter", "fwd partner", "bwd partner", "idle 4", "idle 5",
-                                 "beta recompute", "alpha recompute"};
+  // a wave's phase-A role (row-form filters of chains 4q..4q+3; with
+  // NIPAMD_CK_PHASEA=mfma the phase-B role's own phase A) / its phase-B role.
+  // The filters' phase-B column includes their phase-barrier wait; with
+  // NIPAMD_CK_PHASEA=mfma their columns are 0 / staging / whole kernel.
+  static const char* names[8] = {"fwd rows 0 / fwd filter", "fwd rows 1 / bwd filter", "fwd rows 2 / fwd partner",
+                                 "fwd rows 3 / bwd partner", "bwd rows 0 / bwd post 8-15",
+                                 "bwd rows 1 / fwd post 8-15", "bwd rows 2 / beta recompute",
+                                 "bwd rows 3 / alpha recompute"};
   for (int v = 0; v < 8; v++)
-    std::fprintf(stderr, "[nipamd]   %-16s %9.0f %9.0f %9.0f %9.0f %5.2f %llu\n", names[v], m[v * 5], m[v * 5 + 1],
+    std::fprintf(stderr, "[nipamd]   %-29s %9.0f %9.0f %9.0f %9.0f %5.2f %llu\n", names[v], m[v * 5], m[v * 5 + 1],
                  m[v * 5 + 2], m[v * 5 + 3], m[v * 5 + 4], w[v * 5 + 4]);
 }
 
