@@ -43,6 +43,8 @@ extern "C" {
 #define NIPAMD_STATUS_ZERO_MASS    1u  /* some m2 == 0: ll = -DBL_MAX (src/nip.c:1471-1473) */
 #define NIPAMD_STATUS_BAD_LUCK     2u  /* e_step's m1<=0 || m2<=0 || ll>0 (src/nip.c:1827-1854);
                                           nipamd_estep sets ZERO_MASS|BAD_LUCK */
+#define NIPAMD_STATUS_BAD_EVIDENCE 4u  /* nipamd_fb_soft / nipamd_filter_soft: a likelihood weight that is
+                                          negative, NaN or infinite (set besides ZERO_MASS) */
 
 typedef struct nipamd_model nipamd_model;
 
@@ -589,6 +591,66 @@ void nipamd_stream_free(nipamd_stream* s);
 int nipamd_stream_push_host(nipamd_stream* s, const int32_t* obs, int T, double* post,
                             double* ll, uint32_t* status);
 int nipamd_stream_flush_host(nipamd_stream* s, double* post, double* ll, uint32_t* status);
+
+/*
+ * Batched soft (likelihood) evidence for filtering and smoothing: the
+ * reference's insert_soft_evidence / insert_ucs_step (src/nip.c:967-1030)
+ * multiply a variable's likelihood vector into its clique, and its
+ * uncertain_series lets one model's output become the next model's evidence.
+ * B independent sequences of equal length T, asynchronous on `stream`.
+ *
+ *   d_obs     int32 [B][T][n_obs] hard columns, as nipamd_fb takes them; NULL
+ *             when n_obs == 0
+ *   d_lik     double [B][T][W], W = the summed cardinalities of soft_vars: the
+ *             likelihood vectors of a step, concatenated in soft_vars order --
+ *             the row layout of d_post for query = soft_vars, so rows written
+ *             by nipamd_fb can be fed back in unchanged; NULL when n_soft == 0
+ *   d_post    double [B][T][width], width = the summed cardinalities of query
+ *   d_ll      double [B] or NULL;  d_status uint32 [B] or NULL
+ *
+ * The evidence of step t is the product over the hard columns of the observed
+ * state's table row and over the soft columns of sum_o w[o] E[o][y].  Weights
+ * are likelihoods: non-negative, finite, not necessarily normalised; scaling a
+ * step's vector by c adds log c to ll and changes no row; all ones means "not
+ * observed", a one-hot vector is a hard observation.  A weight that is
+ * negative, NaN or infinite makes its step's evidence zero: the sequence is one
+ * without mass from that step on and gets NIPAMD_STATUS_BAD_EVIDENCE besides
+ * NIPAMD_STATUS_ZERO_MASS.
+ *
+ * Rows, ll and status are those of the streams above with the soft step
+ * evidence: nipamd_filter_soft's rows are the rows of lag 0, nipamd_fb_soft's
+ * those of lag >= T - 1 (all zeros and ll = -DBL_MAX for a sequence that dies
+ * at any step); ll = sum_t log m2_t - log m1_t, m1 the mass under the
+ * all-missing evidence.  A sequence's outputs depend on that sequence's inputs
+ * alone, bit for bit: not on B or on its position in the batch.
+ *
+ * Scope (decided on the host, before the device is touched;
+ * NIPAMD_ERROR_UNSUPPORTED with the condition in nipamd_last_error): a model
+ * with an interface-chain plan, not set to NIPAMD_ENGINE_JTREE; obs_vars and
+ * soft_vars together at most four columns, each the interface variable or a
+ * leaf child, none listed twice; a query that is a non-empty list of distinct
+ * current-slice interface variables (the interface variable, or members of a
+ * joint interface: any subset, any order); tables, the transition and staging
+ * that fit a CU's LDS.  NULL pointers: NIP_ERROR_NULLPOINTER.  B < 1, T < 1, a
+ * variable index out of range: NIP_ERROR_INVALID_ARGUMENT.
+ */
+int nipamd_fb_soft(nipamd_model* m, const int32_t* d_obs, int n_obs, const int* obs_vars,
+                   const double* d_lik, int n_soft, const int* soft_vars,
+                   int B, int T, int n_query, const int* query,
+                   double* d_post, double* d_ll, uint32_t* d_status, void* stream);
+int nipamd_filter_soft(nipamd_model* m, const int32_t* d_obs, int n_obs, const int* obs_vars,
+                       const double* d_lik, int n_soft, const int* soft_vars,
+                       int B, int T, int n_query, const int* query,
+                       double* d_post, double* d_ll, uint32_t* d_status, void* stream);
+/* Host-buffer forms (copy in and out and synchronise). */
+int nipamd_fb_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, const int* obs_vars,
+                        const double* lik, int n_soft, const int* soft_vars,
+                        int B, int T, int n_query, const int* query,
+                        double* post, double* ll, uint32_t* status);
+int nipamd_filter_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, const int* obs_vars,
+                            const double* lik, int n_soft, const int* soft_vars,
+                            int B, int T, int n_query, const int* query,
+                            double* post, double* ll, uint32_t* status);
 
 #ifdef __cplusplus
 }

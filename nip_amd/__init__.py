@@ -21,6 +21,8 @@ from . import build as _build
 __all__ = ["NipError", "Model", "parse_model", "lib", "forward_backward_inference",
            "forward_backward_inference_host", "forward_inference", "forward_inference_host",
            "most_likely_states", "most_likely_states_host", "Stream",
+           "forward_backward_inference_soft", "forward_inference_soft",
+           "forward_backward_inference_soft_host", "forward_inference_soft_host",
            "e_step", "estep_partial", "estep_finalize", "em_learn", "read_timeseries",
            "write_uncertainseries", "write_model", "em_learn_series", "LIB_PATH"]
 
@@ -39,6 +41,7 @@ NIPAMD_ERROR_UNSUPPORTED = 100
 NIPAMD_ERROR_DEVICE = 101
 STATUS_ZERO_MASS = 1
 STATUS_BAD_LUCK = 2
+STATUS_BAD_EVIDENCE = 4  # NIPAMD_STATUS_BAD_EVIDENCE: a soft-evidence weight negative, NaN or infinite
 ENGINE_AUTO = 0          # interface-chain kernels where they apply, else the general engine
 ENGINE_CHAIN = 1         # interface-chain kernels only
 ENGINE_JTREE = 2         # the general join-tree engine for every request
@@ -69,6 +72,7 @@ EXPORTS = [
     "nipamd_stream_open", "nipamd_stream_push", "nipamd_stream_flush", "nipamd_stream_reset",
     "nipamd_stream_pending", "nipamd_stream_steps", "nipamd_stream_free",
     "nipamd_stream_push_host", "nipamd_stream_flush_host",
+    "nipamd_fb_soft", "nipamd_filter_soft", "nipamd_fb_soft_host", "nipamd_filter_soft_host",
 ]
 
 
@@ -109,6 +113,11 @@ def lib():
         L.nipamd_filter_host.argtypes = L.nipamd_fb_host.argtypes
         L.nipamd_mlss.argtypes = L.nipamd_fb.argtypes
         L.nipamd_mlss_host.argtypes = L.nipamd_fb_host.argtypes
+        L.nipamd_fb_soft.argtypes = [vp, vp, C.c_int, ip, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip,
+                                     vp, vp, vp, vp]
+        L.nipamd_filter_soft.argtypes = L.nipamd_fb_soft.argtypes
+        L.nipamd_fb_soft_host.argtypes = L.nipamd_fb_soft.argtypes[:-1]
+        L.nipamd_filter_soft_host.argtypes = L.nipamd_fb_soft_host.argtypes
         L.nipamd_stream_open.argtypes = [vp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.POINTER(vp)]
         L.nipamd_stream_push.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
         L.nipamd_stream_flush.argtypes = [vp, vp, vp, vp, vp]
@@ -423,6 +432,116 @@ def forward_backward_inference_host(model: Model, obs, obs_vars, query):
 def forward_inference_host(model: Model, obs, obs_vars, query):
     """forward_inference from host numpy buffers (PCIe-inclusive, synchronous)."""
     return _run_host(lib().nipamd_filter_host, model, obs, obs_vars, query)
+
+
+def _run_soft_device(fn, model, obs, obs_vars, lik, soft_vars, query, post, ll, status, stream):
+    """obs (None when obs_vars is empty and lik is given) and lik (None when
+    soft_vars is empty) must be exactly what the kernel reads through their raw
+    pointers; B and T come from whichever is given."""
+    import torch
+    W = sum(model.card(v) for v in soft_vars)
+    width = sum(model.card(v) for v in query)
+    shape = None
+    if lik is not None or len(soft_vars):
+        if (not torch.is_tensor(lik) or lik.dtype != torch.float64 or not lik.is_cuda or not lik.is_contiguous()
+                or lik.dim() != 3 or lik.shape[2] != W):
+            got = " (got %s %s on %s)" % (lik.dtype, tuple(lik.shape), lik.device) if torch.is_tensor(lik) else ""
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT,
+                           "lik must be a contiguous float64 CUDA tensor of shape (B, T, %d)%s" % (W, got))
+        shape, dev = (int(lik.shape[0]), int(lik.shape[1])), lik.device
+    if obs is None:
+        if len(obs_vars) or shape is None:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs may be None only when obs_vars is empty and lik is given")
+    else:
+        if torch.is_tensor(obs) and obs.dim() == 2:
+            obs = obs.unsqueeze(-1)
+        if (not torch.is_tensor(obs) or obs.dtype != torch.int32 or not obs.is_cuda or not obs.is_contiguous()
+                or obs.dim() != 3 or obs.shape[2] != len(obs_vars)
+                or (shape is not None and (tuple(obs.shape[:2]) != shape or obs.device != dev))):
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT,
+                           "obs must be a contiguous int32 CUDA tensor of shape (B, T, %d), B and T and the device "
+                           "as lik's" % len(obs_vars))
+        shape, dev = (int(obs.shape[0]), int(obs.shape[1])), obs.device
+    B, T = shape
+    post = _out_buf(post, (B, T, width), torch.float64, dev, "post")
+    ll = _out_buf(ll, (B,), torch.float64, dev, "ll")
+    status = _out_buf(status, (B,), torch.int32, dev, "status")
+    _check(fn(model._h, C.c_void_p(obs.data_ptr() if len(obs_vars) else 0), len(obs_vars), _ints(obs_vars),
+              C.c_void_p(lik.data_ptr() if len(soft_vars) else 0), len(soft_vars), _ints(soft_vars), B, T,
+              len(query), _ints(query), C.c_void_p(post.data_ptr()), C.c_void_p(ll.data_ptr()),
+              C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+    return post, ll, status
+
+
+def _run_soft_host(fn, model, obs, obs_vars, lik, soft_vars, query):
+    W = sum(model.card(v) for v in soft_vars)
+    width = sum(model.card(v) for v in query)
+    B = T = None
+    if lik is not None:
+        lik = np.ascontiguousarray(np.asarray(lik, np.float64))
+        if lik.ndim != 3 or lik.shape[2] != W:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "lik must have shape (B, T, %d) (got %s)" % (W, lik.shape))
+        B, T = lik.shape[:2]
+    elif len(soft_vars):
+        raise NipError(NIP_ERROR_INVALID_ARGUMENT, "lik must have shape (B, T, %d)" % W)
+    if obs is not None:
+        obs = np.ascontiguousarray(np.asarray(obs, np.int32))
+        if obs.ndim == 2:
+            obs = obs[:, :, None]
+        if obs.ndim != 3 or obs.shape[2] != len(obs_vars) or (B is not None and obs.shape[:2] != (B, T)):
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs must have shape (%s, %s, %d) (got %s)"
+                           % ("B" if B is None else B, "T" if T is None else T, len(obs_vars), obs.shape))
+        B, T = obs.shape[:2]
+    elif len(obs_vars) or B is None:
+        raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs may be None only when obs_vars is empty and lik is given")
+    post = np.zeros((B, T, width))
+    ll = np.zeros(B)
+    status = np.zeros(B, np.uint32)
+    _check(fn(model._h, obs.ctypes.data_as(C.c_void_p) if obs is not None and len(obs_vars) else None, len(obs_vars),
+              _ints(obs_vars), lik.ctypes.data_as(C.c_void_p) if lik is not None and len(soft_vars) else None,
+              len(soft_vars), _ints(soft_vars), B, T, len(query), _ints(query), post.ctypes.data_as(C.c_void_p),
+              ll.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+    return post, ll, status
+
+
+def forward_backward_inference_soft(model: Model, obs, obs_vars, lik, soft_vars, query, post=None, ll=None,
+                                    status=None, stream=None):
+    """Batched smoothing under hard and soft (likelihood) evidence on the GPU
+    (nipamd_fb_soft; the reference's insert_soft_evidence, src/nip.c:967-1030).
+
+    obs: torch int32 CUDA tensor [B, T, len(obs_vars)] (state index, <0
+    missing), or None when obs_vars is empty.  lik: contiguous float64 CUDA
+    tensor [B, T, W], W = sum card(soft_vars): each step's likelihood vectors
+    in soft_vars order -- the row layout of ``post`` for query = soft_vars, so
+    the rows of forward_backward_inference can be fed back in; None when
+    soft_vars is empty.  Weights are non-negative and finite, not necessarily
+    normalised (all ones: not observed; one-hot: a hard observation); a
+    negative, NaN or infinite weight leaves its sequence without mass from that
+    step on, with STATUS_BAD_EVIDENCE | STATUS_ZERO_MASS.  query: the model's
+    interface variable, or members of a joint interface (any subset, any order).
+    Returns (post [B, T, sum card(query)], ll [B], status [B]), CUDA tensors,
+    computed asynchronously on ``stream`` (default: torch's current stream)."""
+    return _run_soft_device(lib().nipamd_fb_soft, model, obs, obs_vars, lik, soft_vars, query, post, ll, status,
+                            stream)
+
+
+def forward_inference_soft(model: Model, obs, obs_vars, lik, soft_vars, query, post=None, ll=None, status=None,
+                           stream=None):
+    """Batched filtering under hard and soft evidence (nipamd_filter_soft):
+    P(X_t | evidence of steps 0..t) and the same ll.  Buffers and conventions
+    as forward_backward_inference_soft."""
+    return _run_soft_device(lib().nipamd_filter_soft, model, obs, obs_vars, lik, soft_vars, query, post, ll, status,
+                            stream)
+
+
+def forward_backward_inference_soft_host(model: Model, obs, obs_vars, lik, soft_vars, query):
+    """forward_backward_inference_soft from host numpy buffers (PCIe-inclusive, synchronous)."""
+    return _run_soft_host(lib().nipamd_fb_soft_host, model, obs, obs_vars, lik, soft_vars, query)
+
+
+def forward_inference_soft_host(model: Model, obs, obs_vars, lik, soft_vars, query):
+    """forward_inference_soft from host numpy buffers (PCIe-inclusive, synchronous)."""
+    return _run_soft_host(lib().nipamd_filter_soft_host, model, obs, obs_vars, lik, soft_vars, query)
 
 
 def most_likely_states(model: Model, obs, obs_vars, query, path=None, logp=None, status=None,

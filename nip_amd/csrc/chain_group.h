@@ -1,5 +1,6 @@
-// chain_group.h -- the lane-group layout of chain_viterbi_kernel (viterbi.hip)
-// and chain_stream_kernel (stream.hip): device helpers and the launch ladder.
+// chain_group.h -- the lane-group layout of chain_viterbi_kernel (viterbi.hip),
+// chain_stream_kernel (stream.hip) and chain_soft_kernel (soft.hip): device
+// helpers, the forward step of the latter two, and the launch ladder.
 //
 // NP = 16, 32 or 64 padded states, one NP-lane group per sequence, lane y =
 // state y, 64 / NP sequences per wave, kGroupWaves independent waves per block:
@@ -48,6 +49,62 @@ __device__ __forceinline__ double group_max(double x) {
   return x;
 }
 
+// sum_k v[lane k of the group] c_k for this lane: c = this lane's 16 coefficients
+// in registers (NP = 16), or column `y` of the LDS image Al [k][NP] above that,
+// v passing through the wave's LDS row xch.  A fixed k order.
+template <int NP>
+__device__ __forceinline__ double matvec(double v, const double (&c)[16], const double* Al, double* xch, int lane,
+                                         int gbase, int y) {
+  if constexpr (NP == 16) {
+    return dot_bcast(v, c);
+  } else {
+    xch[lane] = v;
+    wave_lds_sync();
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < NP; k += 4) {
+      a0 = fma(xch[gbase + k], Al[k * NP + y], a0);
+      a1 = fma(xch[gbase + k + 1], Al[(k + 1) * NP + y], a1);
+      a2 = fma(xch[gbase + k + 2], Al[(k + 2) * NP + y], a2);
+      a3 = fma(xch[gbase + k + 3], Al[(k + 3) * NP + y], a3);
+    }
+    wave_lds_sync();
+    return (a0 + a1) + (a2 + a3);
+  }
+}
+
+// the running totals of one sequence (the same values in every lane of its group)
+struct Totals {
+  double num, den;   // mantissas in [0.5, 1) of the products of the m2 and of the m1
+  long ex;           // the products' exponents, num's minus den's
+  unsigned status;
+  long dead;      // the first step without mass, kStreamAlive while there is none
+};
+
+// One forward step at step t: al = alpha^_{t-1} -> alpha^_t under the evidence e.
+// LL: the head's step, which also carries the totals.
+template <int NP, bool LL>
+__device__ __forceinline__ double fwd_step(double al, double e, double sall, const double (&Ac)[16], const double* Af,
+                                           double* xch, int lane, int gbase, int y, long t, Totals& tot) {
+  const double u = matvec<NP>(al, Ac, Af, xch, lane, gbase, y);
+  const double a = u * e;
+  const double m2 = group_sum<NP>(a);
+  const bool ok = m2 > 0.0;
+  if constexpr (LL) {
+    const double m1 = group_sum<NP>(u * sall);
+    if (ok) {
+      int e2 = 0, e1 = 0;
+      tot.num = frexp(tot.num * m2, &e2);
+      tot.den = frexp(tot.den * m1, &e1);
+      tot.ex += e2 - e1;
+    } else {
+      if (tot.dead == kStreamAlive) tot.dead = t;
+      tot.status |= 1u;
+    }
+  }
+  return ok ? a / m2 : 0.0;
+}
+
 // The block stages the NC evidence tables into tabs as [rows][NP] -- column k's
 // M_k + 2 rows from row0[k] on -- and ebase as the row after them; returns that
 // row (tabs + rows NP; evid_rows(a) rows with it).  The caller's block barrier
@@ -76,7 +133,7 @@ inline size_t evid_rows(const EvidenceArgs& a) {
   return rows;
 }
 
-// the shapes both launchers refuse (a: ViterbiArgs or StreamArgs)
+// the shapes every launcher refuses (a: ViterbiArgs, StreamArgs or SoftArgs)
 template <typename Args>
 bool cols_shape_ok(const Args& a) {
   if (a.N < 1 || a.N > 64 || a.ncol < 0 || a.ncol > 4 || a.nq < 0 || a.nq > kViterbiMaxQuery || a.B < 1 ||

@@ -295,6 +295,42 @@ int chain_stream_launch(const StreamArgs& a, hipStream_t stream);
 // base = head = pi, ll = 0, status = 0, no dead step
 int chain_stream_init_launch(const StreamArgs& a, const double* pi64, hipStream_t stream);
 
+// soft (likelihood) evidence (soft.hip, chain_soft_kernel): filtering and
+// smoothing of whole sequences whose step evidence is a product of table rows
+// (hard columns, as everywhere) and of weighted sums of table rows
+// sum_o w[o] E[o][y] (soft columns: one likelihood vector per step).  The
+// evidence columns 0 .. nhard - 1 are hard -- col[k] is their column in obs --
+// and nhard .. ncol - 1 soft -- col[k] is where their M[k] weights start in a
+// row of lik.  Rows, ll and status as chain_stream_kernel defines them (lag 0:
+// filter; lag >= T - 1: fb); a weight that is negative, NaN or infinite leaves
+// its step without evidence mass and sets kSoftBadEvidence.
+constexpr unsigned kSoftBadEvidence = 4u;
+struct SoftArgs : EvidenceArgs {
+  const double* A;       // [64][64]
+  const double* sall;    // [64] product of every child's row sums
+  const double* pi;      // [64] prior of the previous slice
+  long B;
+  int T, N;
+  int nhard;             // hard columns (the first ones)
+  const double* lik;     // double [B][T][W] likelihood vectors, or nullptr (nhard == ncol)
+  long lik_bstride;      // elements between sequences
+  int lik_tstride;       // elements between time steps (W)
+  double* S;             // fb: alpha^_t [B][T][NP], chain_soft_scratch_bytes
+  double* post;          // rows [B][T][width]
+  long post_bstride;     // elements between sequences
+  int post_tstride;      // elements between rows (width)
+  int nq;                // queried variables; nq == 0: the interface state itself (width N)
+  int qstride[kViterbiMaxQuery], qcard[kViterbiMaxQuery];
+  double* ll;            // [B] or nullptr
+  unsigned* status;      // [B] or nullptr
+  int filter;            // 1: the filtered rows, no scratch
+};
+size_t chain_soft_scratch_bytes(int N, long B, int T);
+size_t chain_soft_lds_bytes(const SoftArgs& a);
+// the dynamic-LDS limit of the kernel that serves a (ensure_dyn_lds): 0, or a refusal / failure
+int chain_soft_prepare(const SoftArgs& a);
+int chain_soft_launch(const SoftArgs& a, hipStream_t stream);
+
 // generate_data (generate.hip): one sampling step per variable, in sampling
 // order.  In the first slice the conditional row of step i starts at
 // tab[off0 + idx], idx = sum_c value(ctx[c]) * stride[c] (in elements) with

@@ -52,62 +52,6 @@ namespace nipamd {
 
 namespace {
 
-// sum_k v[lane k of the group] c_k for this lane: c = this lane's 16 coefficients
-// in registers (NP = 16), or column `y` of the LDS image Al [k][NP] above that,
-// v passing through the wave's LDS row xch.  A fixed k order.
-template <int NP>
-__device__ __forceinline__ double matvec(double v, const double (&c)[16], const double* Al, double* xch, int lane,
-                                         int gbase, int y) {
-  if constexpr (NP == 16) {
-    return dot_bcast(v, c);
-  } else {
-    xch[lane] = v;
-    wave_lds_sync();
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < NP; k += 4) {
-      a0 = fma(xch[gbase + k], Al[k * NP + y], a0);
-      a1 = fma(xch[gbase + k + 1], Al[(k + 1) * NP + y], a1);
-      a2 = fma(xch[gbase + k + 2], Al[(k + 2) * NP + y], a2);
-      a3 = fma(xch[gbase + k + 3], Al[(k + 3) * NP + y], a3);
-    }
-    wave_lds_sync();
-    return (a0 + a1) + (a2 + a3);
-  }
-}
-
-// the running totals of one sequence (the same values in every lane of its group)
-struct Totals {
-  double num, den;   // mantissas in [0.5, 1) of the products of the m2 and of the m1
-  long ex;           // the products' exponents, num's minus den's
-  unsigned status;
-  long dead;      // the first step without mass, kStreamAlive while there is none
-};
-
-// One forward step at step t: al = alpha^_{t-1} -> alpha^_t under the evidence e.
-// LL: the head's step, which also carries the totals.
-template <int NP, bool LL>
-__device__ __forceinline__ double fwd_step(double al, double e, double sall, const double (&Ac)[16], const double* Af,
-                                           double* xch, int lane, int gbase, int y, long t, Totals& tot) {
-  const double u = matvec<NP>(al, Ac, Af, xch, lane, gbase, y);
-  const double a = u * e;
-  const double m2 = group_sum<NP>(a);
-  const bool ok = m2 > 0.0;
-  if constexpr (LL) {
-    const double m1 = group_sum<NP>(u * sall);
-    if (ok) {
-      int e2 = 0, e1 = 0;
-      tot.num = frexp(tot.num * m2, &e2);
-      tot.den = frexp(tot.den * m1, &e1);
-      tot.ex += e2 - e1;
-    } else {
-      if (tot.dead == kStreamAlive) tot.dead = t;
-      tot.status |= 1u;
-    }
-  }
-  return ok ? a / m2 : 0.0;
-}
-
 template <int NP, int NC>
 __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_kernel(StreamArgs a) {
   constexpr int G = 64 / NP;
