@@ -610,12 +610,20 @@ int nipamd_stream_flush_host(nipamd_stream* s, double* post, double* ll, uint32_
  *
  * The evidence of step t is the product over the hard columns of the observed
  * state's table row and over the soft columns of sum_o w[o] E[o][y].  Weights
- * are likelihoods: non-negative, finite, not necessarily normalised; scaling a
- * step's vector by c adds log c to ll and changes no row; all ones means "not
- * observed", a one-hot vector is a hard observation.  A weight that is
- * negative, NaN or infinite makes its step's evidence zero: the sequence is one
- * without mass from that step on and gets NIPAMD_STATUS_BAD_EVIDENCE besides
- * NIPAMD_STATUS_ZERO_MASS.
+ * are likelihoods, not necessarily normalised.  Accepted: any vector of finite,
+ * non-negative weights with a positive entry, at any scale from denormals to
+ * DBL_MAX (densities of 1e-300 or 1e+200 need no care of the caller's).  Each
+ * vector is used at the scale of its largest weight, an exact power of two that
+ * goes into ll, and the product of the weights as given is never formed: so
+ * scaling a step's vector by c adds log c to ll and changes no row -- for c a
+ * power of two not one bit of a row, as long as c w stays normal -- and
+ * nothing overflows or underflows on the way.  All ones means "not observed", a
+ * one-hot vector is a hard observation.  A step is without mass only where its
+ * evidence is truly zero: an all-zero vector, or no overlap of the vectors with
+ * the states the chain can be in (NIPAMD_STATUS_ZERO_MASS), never because the
+ * weights are small.  A weight that is negative, NaN or infinite makes its
+ * step's evidence zero: the sequence is one without mass from that step on and
+ * gets NIPAMD_STATUS_BAD_EVIDENCE besides NIPAMD_STATUS_ZERO_MASS.
  *
  * Rows, ll and status are those of the streams above with the soft step
  * evidence: nipamd_filter_soft's rows are the rows of lag 0, nipamd_fb_soft's

@@ -10,8 +10,12 @@
 //   e_t[y] = ebase[y]  prod_hard E_k[o_{k,t}][y]  prod_soft sum_o w_{k,t}[o] E_k[o][y]
 //
 // -- all ones gives the "missing" row, a one-hot vector a hard observation, and
-// scaling a step's vector by c adds log c to the ll.  Everything else is
-// stream.hip's recursion on a whole sequence:
+// scaling a step's vector by c adds log c to the ll and moves no row, for any
+// finite non-negative vector with a positive entry (denormals to DBL_MAX): a
+// vector is used at the scale of its largest weight and the power of two taken
+// out goes to the ll's exponent (evid below), so e_t is a product of factors of
+// ordinary size.  Everything else is stream.hip's recursion on a whole sequence
+// (DESIGN.md 2):
 //
 //   forward   alpha^_t = fwd_step(alpha^_{t-1}, e_t), alpha^_{-1} = prior; the ll as
 //             two mantissa products and one exponent (chain_group.h)
@@ -118,11 +122,19 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
       else s.w[k] = lrow[(long)t * a.lik_tstride + a.col[k] + (y < a.M[k] ? y : 0)];
     }
   };
-  // e_t of this lane's state from the step's loads; bad: a weight of the group's
-  // sequence is negative, NaN or infinite (then e_t = 0)
-  auto evid = [&](int t, const Step& s, bool& bad) {
+  // e_t of this lane's state from the step's loads, every soft vector taken at
+  // the scale of its largest weight: w 2^-ex with 2^(ex-1) <= max w < 2^ex
+  // (frexp / ldexp: exact), so that a column's sum is of the size of its table's
+  // entries whatever the caller's scale, the product over the columns neither
+  // overflows nor underflows on the way, and the rows are the same bits for w
+  // and for 2^k w.  exs: the sum of the columns' ex, which the forward pass adds
+  // to the ll's exponent (the backward pass normalises and needs none).  bad: a
+  // weight of the group's sequence is negative, NaN or infinite (then e_t = 0);
+  // such a weight is 0 before the maximum is taken.
+  auto evid = [&](int t, const Step& s, bool& bad, long& exs) {
     double e = eb[y];
     bool mine = false;
+    exs = 0;
 #pragma unroll
     for (int k = 0; k < NC; k++) {
       if (k < NH) {
@@ -130,21 +142,35 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
       } else {
         const int M = a.M[k];
         const double* tk = tabs + row0[k] * NP + y;
+        // this lane's weight of the piece from c0 on, a bad one as 0 (past the
+        // vector's end: its first weight again, which cannot raise the maximum)
+        auto valid = [&](double w, int c0) {
+          const bool wb = !(w >= 0.0 && w <= DBL_MAX);
+          mine |= wb && c0 + y < M;
+          return wb ? 0.0 : w;
+        };
+        auto later = [&](int c0) {
+          return lrow[(long)t * a.lik_tstride + a.col[k] + (c0 + y < M ? c0 + y : 0)];
+        };
+        const double w0 = valid(s.w[k], 0);
+        double mx = w0;
+        if constexpr (LONG)
+          for (int c0 = NP; c0 < M; c0 += NP) mx = fmax(mx, valid(later(c0), c0));
+        int ex = 0;
+        (void)frexp(group_max<NP>(mx), &ex);               // 0 for a maximum of 0
+        exs += ex;
         double acc = 0.0;
-        // the weights o = c0 .. c0 + n - 1, this lane's being w (its first weight again past the vector's end)
+        // the weights o = c0 .. c0 + n - 1, this lane's being w
         auto piece = [&](double w, int c0) {
-          const bool wb = c0 + y < M && !(w >= 0.0 && w <= DBL_MAX);
-          mine |= wb;
-          wrow[lane] = wb ? 0.0 : w;
+          wrow[lane] = ldexp(w, -ex);
           wave_lds_sync();
           const int n = M - c0 < NP ? M - c0 : NP;
           for (int o = 0; o < n; o++) acc = fma(wrow[gbase + o], tk[(c0 + o) * NP], acc);
           wave_lds_sync();
         };
-        piece(s.w[k], 0);
+        piece(w0, 0);
         if constexpr (LONG)
-          for (int c0 = NP; c0 < M; c0 += NP)
-            piece(lrow[(long)t * a.lik_tstride + a.col[k] + (c0 + y < M ? c0 + y : 0)], c0);
+          for (int c0 = NP; c0 < M; c0 += NP) piece(valid(later(c0), c0), c0);
         e *= acc;
       }
     }
@@ -205,8 +231,10 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
       fetch(t + 1 < T ? t + 1 : t, nxt);
       if (t > 0) store(t - 1);
       bool bad;
-      const double e = evid(t, cur, bad);
+      long exs;
+      const double e = evid(t, cur, bad, exs);
       hd = fwd_step<NP, true>(hd, e, sall, Ac, Af, xch, lane, gbase, y, t, tot);
+      tot.ex += exs;                                       // m2 of the weights as given is 2^exs times fwd_step's
       if (bad) tot.status |= kSoftBadEvidence;
       owed = decltype(filter)::value ? value(hd, false, tot.dead != kStreamAlive) : hd;
       cur = nxt;
@@ -233,7 +261,8 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
     const double aln = t > 0 ? srow[(long)(t - 1) * NP] : 0.0;
     put(owed, t + 1);
     bool bad;
-    const double e = evid(t + 1, cur, bad);
+    long exs;
+    const double e = evid(t + 1, cur, bad, exs);
     beta = matvec<NP>(e * beta, Ar, Ab, xch, lane, gbase, y);
     int ex = 0;
     (void)frexp(group_max<NP>(beta), &ex);                 // 0 for a maximum of 0

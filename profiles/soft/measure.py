@@ -1,7 +1,9 @@
 """Soft evidence against hard evidence on hmm_spec(16, 16), M1 soft, B = 4096,
 T = 1024 ("Soft evidence"): one process, every variant warmed up,
 then 30 launches each, alternating, a pair of device events around each
-launch; median, min..max.  Usage: python profiles/soft/measure.py [out.json]"""
+launch; median, min..max.  Usage: python profiles/soft/measure.py [out.json]
+(NIPAMD_LIB selects another build of the library: measure.json holds three such
+runs each of two builds, alternating, merged per call)."""
 import json
 import os
 import sys

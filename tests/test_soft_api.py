@@ -2,7 +2,9 @@
 host forms) without a GPU: the exported symbols, the argument and scope
 verdicts (decided on the host, before anything touches the device), and the
 numpy oracle of tests/test_gpu_soft.py (soft_util.soft_smoother) pinned to
-textbook_util.smoother."""
+textbook_util.smoother and, on the inputs of tests/test_gpu_soft_scale.py
+(weights from denormal to DBL_MAX), to a wide-exponent evaluation of the same
+recursion that takes no scale out of anything (wide_smoother below)."""
 import ctypes as C
 import os
 import re
@@ -13,6 +15,8 @@ import pytest
 import nip_amd
 from nip_amd import synth
 
+import small_mass_util as sm
+import soft_scale_util as ssu
 import soft_util as so
 from textbook_util import smoother
 
@@ -262,3 +266,215 @@ def test_dead_sequences_and_bad_weights():
         assert not np.isnan(post).any() and not np.isnan(filt).any() and not np.isnan(ll).any()
         for k in (0, 2, 3):
             assert np.array_equal(post[k], good[0][k]) and ll[k] == good[2][k]
+
+
+# ---------------------------------------------------------------------------
+# the oracle at every weight scale, pinned to a wide-exponent evaluation
+#
+# wide_smoother is the recursion of soft_util._run written out again with the
+# weights as given -- no exponent taken out, e_t the plain product -- in a
+# number format whose exponent range holds every product these inputs form
+# (four columns at DBL_MAX: 2^4096): np.longdouble where it is the x87 80-bit
+# format (maxexp 16384, 64-bit mantissa), mpmath at 50 digits elsewhere.
+
+def wide_backend():
+    return "longdouble" if np.finfo(np.longdouble).maxexp > 1024 else "mpmath"
+
+
+def wide_ops(backend):
+    """(to, log, back): float64 array -> wide array, the elementwise logarithm
+    of positive wide numbers, wide array -> float64."""
+    if backend == "longdouble":
+        return (lambda a: np.asarray(a, np.longdouble)), np.log, (lambda a: np.asarray(a, np.float64))
+    import mpmath
+    ctx = mpmath.MPContext()
+    ctx.dps = 50
+    to = np.frompyfunc(lambda x: ctx.mpf(float(x)), 1, 1)
+    log = np.frompyfunc(ctx.log, 1, 1)
+    back = lambda a: np.frompyfunc(float, 1, 1)(a).astype(np.float64)
+    return (lambda a: to(np.asarray(a, np.float64))), log, back
+
+
+def wide_smoother(A, pi, Es, kinds, cols, liks, backend=None):
+    """(smoothed, filtered, ll, status) as float64 / int64 arrays, soft_util's
+    definitions (a dead sequence: ll = -DBL_MAX, zero rows from its dead step
+    on, all smoothed rows zero; status 1, plus 4 for a bad weight)."""
+    to, log, back = wide_ops(backend or wide_backend())
+    Aw, Ew = to(A), [to(E) for E in Es]
+    T = next(c.shape[1] for kind, c in zip(kinds, cols) if kind == so.HARD) if so.HARD in kinds else \
+        next(w.shape[1] for kind, w in zip(kinds, liks) if kind == so.SOFT)
+    B = next(c.shape[0] for kind, c in zip(kinds, cols) if kind == so.HARD) if so.HARD in kinds else \
+        next(w.shape[0] for kind, w in zip(kinds, liks) if kind == so.SOFT)
+    N = A.shape[0]
+    zero, one = to(np.zeros((1, 1))), to(np.ones((1, 1)))
+    s_all = one[0] * to(np.ones(N))
+    for E in Ew:
+        s_all = s_all * E.sum(axis=1)
+
+    def ev(t):
+        e = one * to(np.ones((B, N)))
+        bad = np.zeros(B, bool)
+        for E, kind, c, w in zip(Ew, kinds, cols, liks):
+            if kind == so.HARD:
+                x, M = c[:, t], E.shape[1]
+                f = E[:, np.clip(x, 0, M - 1)].T
+                f = np.where((x < 0)[:, None], E.sum(axis=1)[None, :], f)
+                f = np.where((x >= M)[:, None], zero, f)
+            else:
+                wt = np.asarray(w[:, t], np.float64)
+                wb = ~(np.isfinite(wt) & (wt >= 0.0))
+                bad |= wb.any(axis=1)
+                f = to(np.where(wb, 0.0, wt)) @ E.T
+            e = e * f
+        return np.where(bad[:, None], zero, e), bad
+
+    evs = [ev(t) for t in range(T)]
+    ah = []
+    ll = to(np.zeros(B))
+    status = np.zeros(B, np.int64)
+    alive = np.ones(B, bool)
+    prev = one * to(np.tile(pi, (B, 1)))
+    for t in range(T):
+        e, bad = evs[t]
+        status[bad] |= 4
+        u = prev @ Aw
+        al = u * e
+        c = al.sum(axis=1)
+        alive &= np.asarray(c > 0, bool)
+        c = np.where(alive, c, one[0])                          # a dead sequence divides by 1 and is zeroed
+        m1 = np.where(alive, (u * s_all).sum(axis=1), one[0])
+        ll = ll + np.where(alive, log(c) - log(m1), zero[0])
+        prev = np.where(alive[:, None], al / c[:, None], zero)
+        ah.append(prev)
+    status[~alive] |= 1
+    post = [None] * T
+    post[T - 1] = ah[T - 1]
+    b = one * to(np.ones((B, N)))
+    for t in range(T - 2, -1, -1):
+        b = (evs[t + 1][0] * b) @ Aw.T
+        b = np.where(alive[:, None], b / np.where(alive, b.sum(axis=1), one[0])[:, None], zero)
+        p = ah[t] * b
+        post[t] = np.where(alive[:, None], p / np.where(alive, p.sum(axis=1), one[0])[:, None], zero)
+    stack = lambda rows: np.stack([back(r) for r in rows], axis=1)
+    post, filt, ll = stack(post), stack(ah), back(ll)
+    post[~alive] = 0.0
+    ll[~alive] = -np.finfo(np.float64).max
+    return post, filt, ll, status
+
+
+PIN_ROWS, PIN_LL, REF_MOVE = 1e-14, 1e-13, 1e-15
+
+
+def usable(ref):
+    """The conditions on an input: the reference alone gives every sequence
+    mass and finite rows."""
+    post, filt, ll, status = ref
+    assert np.all(status == 0), status.tolist()
+    assert np.isfinite(post).all() and np.isfinite(filt).all() and np.isfinite(ll).all()
+
+
+def pinned(got, ref, what):
+    """The fp64 oracle against the reference."""
+    for g in got[:3]:
+        assert np.isfinite(g).all(), what
+    rows = max(np.abs(got[0] - ref[0]).max(), np.abs(got[1] - ref[1]).max())
+    lerr = (np.abs(got[2] - ref[2]) / np.maximum(1.0, np.abs(ref[2]))).max()
+    print("%s: oracle against the wide reference: rows %.3g, ll %.3g (relative)" % (what, rows, lerr))
+    assert rows <= PIN_ROWS, (what, rows)
+    assert lerr <= PIN_LL, (what, lerr)
+    assert np.array_equal(got[3], ref[3]), what
+
+
+@pytest.mark.parametrize("T", ssu.TS)
+@pytest.mark.parametrize("name", ssu.NAMES)
+def test_oracle_at_every_weight_scale(name, T):
+    """Every input of tests/test_gpu_soft_scale.py's scale grid: usable by the
+    reference alone, the reference's rows unmoved by the scaling (1e-15), and
+    the fp64 oracle on the reference (rows 1e-14, ll 1e-13 max(1, |ll|), the
+    same status, everything finite)."""
+    r = ssu.requests()[name]
+    A, pi, Es = r.tables
+    obs, base = ssu.hard_obs(r, T), ssu.base_weights(r, T)
+
+    def both(liks):
+        args = ssu.oracle_args(r, obs, liks)
+        ref = wide_smoother(A, pi, Es, *args)
+        usable(ref)
+        return so._run(A, pi, Es, *args), ref
+
+    got0, ref0 = both(base)
+    pinned(got0, ref0, "unscaled")
+    for big in (560, 530) if name in ssu.TWO_COLUMN else (560,):
+        k = ssu.exponents(T, len(r.soft), big)
+        got, ref = both(ssu.scaled(base, k))
+        move = max(np.abs(ref[0] - ref0[0]).max(), np.abs(ref[1] - ref0[1]).max())
+        print("big = %d: the scaling moves the reference's rows by %.3g" % (big, move))
+        assert move <= REF_MOVE, move
+        pinned(got, ref, "big = %d" % big)
+        # and the oracle's own rows do not see an exact scaling at all
+        assert np.array_equal(got[0], got0[0]) and np.array_equal(got[1], got0[1])
+    pinned(*both(ssu.edge_weights(r, T)), "the edge batch")
+
+
+def test_wide_reference_formats_agree():
+    """The mpmath form of the reference, which a machine whose long double is
+    no wider than double runs, against the long double form where that exists
+    (and against the fp64 oracle on an input of ordinary size elsewhere)."""
+    r = ssu.requests()["demo20-both"]
+    A, pi, Es = r.tables
+    T = 5
+    liks = ssu.scaled(ssu.base_weights(r, T), ssu.exponents(T, 2))
+    args = ssu.oracle_args(r, ssu.hard_obs(r, T), liks)
+    mp = wide_smoother(A, pi, Es, *args, backend="mpmath")
+    usable(mp)
+    other = wide_smoother(A, pi, Es, *args, backend="longdouble") if wide_backend() == "longdouble" else \
+        so._run(A, pi, Es, *args)
+    pinned(other, mp, "mpmath against " + wide_backend())
+
+
+def fed_rows(T=64):
+    """Smoothed rows of test_gpu_soft.two_blocks() under hard evidence: exact
+    zeros on the second block and, towards the end, a shrinking first-block
+    state -- the kind of rows test_gpu_soft_scale feeds back from the device."""
+    import test_gpu_soft as tg
+    _, _, _, (A, pi, Es) = tg.two_blocks()
+    codes = tg.gappy(3, T, (4,), 91)[:, :, 0]
+    codes[codes > 1] -= 2                                   # the first block's symbols
+    return smoother(A, pi, Es, [codes])[0]
+
+
+@pytest.mark.parametrize("shift", [0, -700])
+def test_oracle_on_fed_back_rows(shift):
+    import test_gpu_soft as tg
+    _, _, _, (A, pi, Es) = tg.hmm(4, 4, True)
+    fed = np.ldexp(fed_rows(), shift)
+    assert np.all(fed[:, :, 2:] == 0.0) and np.all(fed[:, :, :2].max(axis=2) > 0.0)
+    args = ([so.HARD, so.SOFT], [np.full(fed.shape[:2], -1), None], [None, fed])
+    ref = wide_smoother(A, pi, Es + [np.eye(4)], *args)
+    usable(ref)
+    pinned(so._run(A, pi, Es + [np.eye(4)], *args), ref, "fed rows 2^%d" % shift)
+
+
+@pytest.mark.parametrize("mu", [1e-80, 1e-150])
+def test_oracle_on_rare_steps_as_weights(mu):
+    """small_mass_util's rare steps as one-hot weights (all ones at a missing
+    step) and with the first column soft beside hard ones: the oracle on the
+    reference and on textbook_util.smoother (1e-13, as the pins above)."""
+    T = 24
+    for c in (sm.rare_hmm(16, 4, mu), sm.rare_star(17, sm.STAR_CARDS, sm.col_scale(mu, 4))):
+        A, pi, Es = c.tables
+        obs = sm.rare_obs(T, c.cards, B=ssu.B)
+        cols = c.cols(obs)
+        want = smoother(A, pi, Es, cols)
+        hot = [np.where((x < 0)[:, :, None], 1.0, np.eye(E.shape[1])[np.maximum(x, 0)]) for E, x in zip(Es, cols)]
+        n = len(Es)
+        for nsoft in (n, 1):
+            kinds = [so.SOFT] * nsoft + [so.HARD] * (n - nsoft)
+            args = (kinds, [None] * nsoft + cols[nsoft:], hot[:nsoft] + [None] * (n - nsoft))
+            ref = wide_smoother(A, pi, Es, *args)
+            usable(ref)
+            got = so._run(A, pi, Es, *args)
+            pinned(got, ref, "mu = %g, %d soft of %d" % (mu, nsoft, n))
+            for g, w in zip(got[:2], want[:2]):
+                assert np.abs(g - w).max() <= 1e-13
+            assert np.all(np.abs(got[2] - want[2]) <= 1e-13 * np.maximum(1.0, np.abs(want[2])))
