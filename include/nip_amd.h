@@ -43,8 +43,9 @@ extern "C" {
 #define NIPAMD_STATUS_ZERO_MASS    1u  /* some m2 == 0: ll = -DBL_MAX (src/nip.c:1471-1473) */
 #define NIPAMD_STATUS_BAD_LUCK     2u  /* e_step's m1<=0 || m2<=0 || ll>0 (src/nip.c:1827-1854);
                                           nipamd_estep sets ZERO_MASS|BAD_LUCK */
-#define NIPAMD_STATUS_BAD_EVIDENCE 4u  /* nipamd_fb_soft / nipamd_filter_soft: a likelihood weight that is
-                                          negative, NaN or infinite (set besides ZERO_MASS) */
+#define NIPAMD_STATUS_BAD_EVIDENCE 4u  /* nipamd_fb_soft / nipamd_filter_soft / nipamd_stream_push_soft: a
+                                          likelihood weight that is negative, NaN or infinite (set besides
+                                          ZERO_MASS) */
 
 typedef struct nipamd_model nipamd_model;
 
@@ -659,6 +660,59 @@ int nipamd_filter_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, cons
                             const double* lik, int n_soft, const int* soft_vars,
                             int B, int T, int n_query, const int* query,
                             double* post, double* ll, uint32_t* status);
+
+/*
+ * Online inference under soft evidence: a stream whose steps bring likelihood
+ * vectors -- a classifier's per-frame scores, a noisy sensor's confusion row,
+ * the rows another stream has just emitted -- as they arrive.
+ *
+ * nipamd_stream_open_soft opens a stream with n_obs hard columns and n_soft
+ * soft ones; the handle is the streams' own and nipamd_stream_flush,
+ * _flush_host, _reset, _pending, _steps and _free serve it.  A push brings
+ *
+ *   d_obs     int32 [B][T][n_obs] hard columns; NULL when n_obs == 0
+ *   d_lik     double [B][T][W], W = the summed cardinalities of soft_vars, the
+ *             row layout and the accepted weights of nipamd_fb_soft; NULL when
+ *             n_soft == 0
+ *
+ * Rows, the emission schedule (E = max(0, pending + T - lag) rows per push,
+ * `pending` rows per flush), ll and the sticky status are those of
+ * nipamd_stream_push with the soft step evidence of nipamd_fb_soft: at lag 0
+ * nipamd_filter_soft's rows, with a lag beyond the stream nipamd_fb_soft's.  A
+ * weight that is negative, NaN or infinite at step d makes the sequence one
+ * without mass from d on, as a zero-mass step does, and sets
+ * NIPAMD_STATUS_BAD_EVIDENCE besides NIPAMD_STATUS_ZERO_MASS.  Rows, ll and
+ * status depend only on the sequence of steps, bit for bit: not on how the
+ * steps were split into pushes, the batch into streams, or on a sequence's
+ * position in the batch.
+ *
+ * A pending step is kept as its evaluated evidence (one double per interface
+ * state): B x (lag + NIPAMD_STREAM_CHUNK) x NP x 8 bytes of device memory per
+ * stream, NP = 16, 32 or 64 padded states -- 64 MB at B = 4096, lag 64 and at
+ * most 16 states; nothing at lag 0.  So a pending step keeps the evidence of
+ * the model's tables as they were at the push that consumed it (a stream of
+ * hard columns keeps the raw codes and reads the tables of every later push).
+ *
+ * Scope (decided at open on the host, arguments before scope): that of
+ * nipamd_stream_open and of nipamd_fb_soft together -- obs_vars and soft_vars
+ * at most four columns, each the interface variable or a leaf child, none
+ * listed twice; tables, the transition and staging that fit a CU's LDS.
+ * n_soft < 0: NIP_ERROR_INVALID_ARGUMENT.  n_soft == 0 opens the stream that
+ * nipamd_stream_open opens.  nipamd_stream_push on a stream with soft columns
+ * is NIP_ERROR_INVALID_ARGUMENT; nipamd_stream_push_soft on one without takes
+ * d_lik == NULL and is nipamd_stream_push.  nipamd_last_kernel reports
+ * "chain_stream_soft_kernel".
+ */
+int nipamd_stream_open_soft(nipamd_model* m, int n_obs, const int* obs_vars,
+                            int n_soft, const int* soft_vars,
+                            int n_query, const int* query, int B, int lag, nipamd_stream** out);
+int nipamd_stream_push_soft(nipamd_stream* s, const int32_t* d_obs /* [B][T][n_obs] or NULL */,
+                            const double* d_lik /* [B][T][W] or NULL */, int T,
+                            double* d_post /* [B][E][width] */, double* d_ll, uint32_t* d_status,
+                            void* stream);
+/* Host-buffer form (copies in and out and synchronises). */
+int nipamd_stream_push_soft_host(nipamd_stream* s, const int32_t* obs, const double* lik, int T,
+                                 double* post, double* ll, uint32_t* status);
 
 #ifdef __cplusplus
 }

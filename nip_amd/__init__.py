@@ -73,6 +73,7 @@ EXPORTS = [
     "nipamd_stream_pending", "nipamd_stream_steps", "nipamd_stream_free",
     "nipamd_stream_push_host", "nipamd_stream_flush_host",
     "nipamd_fb_soft", "nipamd_filter_soft", "nipamd_fb_soft_host", "nipamd_filter_soft_host",
+    "nipamd_stream_open_soft", "nipamd_stream_push_soft", "nipamd_stream_push_soft_host",
 ]
 
 
@@ -129,6 +130,10 @@ def lib():
         L.nipamd_stream_free.restype = None
         L.nipamd_stream_push_host.argtypes = [vp, vp, C.c_int, vp, vp, vp]
         L.nipamd_stream_flush_host.argtypes = [vp, vp, vp, vp]
+        L.nipamd_stream_open_soft.argtypes = [vp, C.c_int, ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int,
+                                              C.POINTER(vp)]
+        L.nipamd_stream_push_soft.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        L.nipamd_stream_push_soft_host.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
         L.nipamd_estep.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_int, vp, vp, vp, vp]
         L.nipamd_estep_partial_size.argtypes = [vp]
         if hasattr(L, "nipamd_estep_partial_size_req"):      # (absent from A/B builds of older revisions)
@@ -604,19 +609,34 @@ class Stream:
     query: the model's interface variable, or members of a joint interface (any
     subset, any order).  The stream keeps its Model alive; close() (or the
     context manager) frees the device state.
+
+    soft_vars: variables whose evidence arrives as likelihood vectors
+    (nipamd_stream_open_soft / nipamd_stream_push_soft): every push then takes
+    ``lik``, float64 [B, T, W] with W = sum card(soft_vars), a step's vectors in
+    soft_vars order -- the weights of forward_backward_inference_soft, and the
+    row layout of another stream's rows for query = soft_vars.  ``obs`` may be
+    None when obs_vars is empty.  A weight that is negative, NaN or infinite
+    sets STATUS_BAD_EVIDENCE | STATUS_ZERO_MASS from its step on.
     """
 
-    def __init__(self, model: Model, obs_vars, query, B: int, lag: int = 0):
+    def __init__(self, model: Model, obs_vars, query, B: int, lag: int = 0, soft_vars=()):
         self._h = None
         self.model = model
         self.obs_vars = [int(v) for v in obs_vars]
+        self.soft_vars = [int(v) for v in soft_vars]
         self.query = [int(v) for v in query]
         self.B, self.lag = int(B), int(lag)
         h = C.c_void_p()
-        _check(lib().nipamd_stream_open(model._h, len(self.obs_vars), _ints(self.obs_vars), len(self.query),
-                                        _ints(self.query), self.B, self.lag, C.byref(h)))
+        if self.soft_vars:
+            _check(lib().nipamd_stream_open_soft(model._h, len(self.obs_vars), _ints(self.obs_vars),
+                                                 len(self.soft_vars), _ints(self.soft_vars), len(self.query),
+                                                 _ints(self.query), self.B, self.lag, C.byref(h)))
+        else:
+            _check(lib().nipamd_stream_open(model._h, len(self.obs_vars), _ints(self.obs_vars), len(self.query),
+                                            _ints(self.query), self.B, self.lag, C.byref(h)))
         self._h = h
         self.width = sum(model.card(v) for v in self.query)
+        self.lik_width = sum(model.card(v) for v in self.soft_vars)
         import torch
         self.ll = torch.zeros((self.B,), dtype=torch.float64, device="cuda")
         self.status = torch.zeros((self.B,), dtype=torch.int32, device="cuda")
@@ -636,10 +656,47 @@ class Stream:
         """Rows still owed: min(steps, lag), 0 after a flush."""
         return lib().nipamd_stream_pending(self._handle())
 
-    def push(self, obs, post=None, stream=None):
-        """obs: torch int32 CUDA tensor [B, T, n_obs] (state index, <0 missing), T >= 1."""
+    def _push_soft(self, obs, lik, post, stream):
+        """push on a stream with soft columns: lik checked as
+        forward_backward_inference_soft checks it, obs against it."""
         import torch
         h = self._handle()
+        W = self.lik_width
+        if (not torch.is_tensor(lik) or lik.dtype != torch.float64 or not lik.is_cuda or not lik.is_contiguous()
+                or lik.dim() != 3 or lik.shape[0] != self.B or lik.shape[2] != W):
+            got = " (got %s %s on %s)" % (lik.dtype, tuple(lik.shape), lik.device) if torch.is_tensor(lik) else ""
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT,
+                           "lik must be a contiguous float64 CUDA tensor of shape (%d, T, %d)%s" % (self.B, W, got))
+        T, dev = int(lik.shape[1]), lik.device
+        if obs is None:
+            if len(self.obs_vars):
+                raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs may be None only when obs_vars is empty")
+        else:
+            if torch.is_tensor(obs) and obs.dim() == 2:
+                obs = obs.unsqueeze(-1)
+            if (not torch.is_tensor(obs) or obs.dtype != torch.int32 or not obs.is_cuda or not obs.is_contiguous()
+                    or obs.dim() != 3 or obs.shape[2] != len(self.obs_vars)
+                    or tuple(obs.shape[:2]) != (self.B, T) or obs.device != dev):
+                raise NipError(NIP_ERROR_INVALID_ARGUMENT,
+                               "obs must be a contiguous int32 CUDA tensor of shape (%d, %d, %d) on lik's device"
+                               % (self.B, T, len(self.obs_vars)))
+        E = max(0, self.pending + T - self.lag)
+        post = _out_buf(post, (self.B, E, self.width), torch.float64, dev, "post")
+        _check(lib().nipamd_stream_push_soft(h, C.c_void_p(obs.data_ptr() if len(self.obs_vars) else 0),
+                                             C.c_void_p(lik.data_ptr()), T, C.c_void_p(post.data_ptr() if E else 0),
+                                             C.c_void_p(self.ll.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                             _stream_ptr(stream)))
+        return post
+
+    def push(self, obs, post=None, stream=None, lik=None):
+        """obs: torch int32 CUDA tensor [B, T, n_obs] (state index, <0 missing), T >= 1;
+        lik: with soft_vars, torch float64 CUDA tensor [B, T, W]."""
+        import torch
+        h = self._handle()
+        if self.soft_vars:
+            return self._push_soft(obs, lik, post, stream)
+        if lik is not None:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "lik given to a stream without soft_vars")
         if obs.dim() == 2:
             obs = obs.unsqueeze(-1)
         if (obs.dtype != torch.int32 or not obs.is_cuda or not obs.is_contiguous() or obs.dim() != 3
@@ -667,9 +724,41 @@ class Stream:
                                          _stream_ptr(stream)))
         return post
 
-    def push_host(self, obs):
-        """push from a host numpy array [B, T, n_obs]: (post, ll, status) as numpy (synchronous)."""
+    def _push_soft_host(self, obs, lik):
         h = self._handle()
+        W = self.lik_width
+        if lik is None:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "lik must have shape (%d, T, %d)" % (self.B, W))
+        lik = np.ascontiguousarray(np.asarray(lik, np.float64))
+        if lik.ndim != 3 or lik.shape[0] != self.B or lik.shape[2] != W:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT,
+                           "lik must have shape (%d, T, %d) (got %s)" % (self.B, W, lik.shape))
+        T = int(lik.shape[1])
+        if obs is not None:
+            obs = np.ascontiguousarray(np.asarray(obs, np.int32))
+            if obs.ndim == 2:
+                obs = obs[:, :, None]
+            if obs.shape != (self.B, T, len(self.obs_vars)):
+                raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs must have shape (%d, %d, %d) (got %s)"
+                               % (self.B, T, len(self.obs_vars), obs.shape))
+        elif len(self.obs_vars):
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs may be None only when obs_vars is empty")
+        post = np.zeros((self.B, max(0, self.pending + T - self.lag), self.width))
+        ll, status = np.zeros(self.B), np.zeros(self.B, np.uint32)
+        _check(lib().nipamd_stream_push_soft_host(
+            h, obs.ctypes.data_as(C.c_void_p) if obs is not None and len(self.obs_vars) else None,
+            lik.ctypes.data_as(C.c_void_p), T, post.ctypes.data_as(C.c_void_p), ll.ctypes.data_as(C.c_void_p),
+            status.ctypes.data_as(C.c_void_p)))
+        return post, ll, status
+
+    def push_host(self, obs, lik=None):
+        """push from host numpy arrays, obs [B, T, n_obs] and with soft_vars lik
+        [B, T, W]: (post, ll, status) as numpy (synchronous)."""
+        h = self._handle()
+        if self.soft_vars:
+            return self._push_soft_host(obs, lik)
+        if lik is not None:
+            raise NipError(NIP_ERROR_INVALID_ARGUMENT, "lik given to a stream without soft_vars")
         obs = np.ascontiguousarray(np.asarray(obs, np.int32))
         if obs.ndim == 2:
             obs = obs[:, :, None]

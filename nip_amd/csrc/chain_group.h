@@ -1,6 +1,7 @@
 // chain_group.h -- the lane-group layout of chain_viterbi_kernel (viterbi.hip),
-// chain_stream_kernel (stream.hip) and chain_soft_kernel (soft.hip): device
-// helpers, the forward step of the latter two, and the launch ladder.
+// chain_stream_kernel (stream.hip), chain_soft_kernel (soft.hip) and
+// chain_stream_soft_kernel (stream_soft.hip): device helpers, the forward step
+// of the latter three, and the launch ladder.
 //
 // NP = 16, 32 or 64 padded states, one NP-lane group per sequence, lane y =
 // state y, 64 / NP sequences per wave, kGroupWaves independent waves per block:
@@ -133,7 +134,7 @@ inline size_t evid_rows(const EvidenceArgs& a) {
   return rows;
 }
 
-// the shapes every launcher refuses (a: ViterbiArgs, StreamArgs or SoftArgs)
+// the shapes every launcher refuses (a: ViterbiArgs, StreamArgs, SoftArgs or StreamSoftArgs)
 template <typename Args>
 bool cols_shape_ok(const Args& a) {
   if (a.N < 1 || a.N > 64 || a.ncol < 0 || a.ncol > 4 || a.nq < 0 || a.nq > kViterbiMaxQuery || a.B < 1 ||

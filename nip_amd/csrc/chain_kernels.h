@@ -331,6 +331,29 @@ size_t chain_soft_lds_bytes(const SoftArgs& a);
 int chain_soft_prepare(const SoftArgs& a);
 int chain_soft_launch(const SoftArgs& a, hipStream_t stream);
 
+// online inference under soft evidence (stream_soft.hip,
+// chain_stream_soft_kernel): chain_stream_kernel's launch over SoftArgs'
+// evidence columns -- 0 .. nhard - 1 hard, col[k] their column in obs; nhard ..
+// ncol - 1 soft, col[k] where their M[k] weights start in a row of lik.  A
+// likelihood vector has no code to keep, so in place of StreamArgs' ring of raw
+// codes (unused here) the state holds the evaluated evidence e_t[y] of the
+// window's steps, NP doubles each: step t in slot t % R, R = lag +
+// kStreamChunk, so that one launch's window (pending, then new steps) never
+// meets itself.  B R NP 8 bytes: 64 MB at B = 4096, lag 64, N <= 16.  No ring
+// at lag 0.
+struct StreamSoftArgs : StreamArgs {
+  int nhard;             // hard columns (the first ones)
+  const double* lik;     // double [B][T_new ..][W] likelihood vectors of the new steps, or nullptr (nhard == ncol)
+  long lik_bstride;      // elements between sequences
+  int lik_tstride;       // elements between time steps (W)
+  double* ering;         // [B][R][NP] the window's e_t, or nullptr (lag 0)
+};
+inline size_t chain_stream_soft_ring_slots(int lag) { return lag > 0 ? (size_t)lag + kStreamChunk : 0; }
+size_t chain_stream_soft_lds_bytes(const StreamSoftArgs& a);
+// the dynamic-LDS limit of the kernel that serves a (ensure_dyn_lds): 0, or a refusal / failure
+int chain_stream_soft_prepare(const StreamSoftArgs& a);
+int chain_stream_soft_launch(const StreamSoftArgs& a, hipStream_t stream);
+
 // generate_data (generate.hip): one sampling step per variable, in sampling
 // order.  In the first slice the conditional row of step i starts at
 // tab[off0 + idx], idx = sum_c value(ctx[c]) * stride[c] (in elements) with
