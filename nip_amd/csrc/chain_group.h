@@ -1,7 +1,8 @@
 // chain_group.h -- the lane-group layout of chain_viterbi_kernel (viterbi.hip),
 // chain_stream_kernel (stream.hip), chain_soft_kernel (soft.hip) and
 // chain_stream_soft_kernel (stream_soft.hip): device helpers, the forward step
-// of the latter three, and the launch ladder.
+// of the latter three, and the launch ladder.  What only those three share is
+// soft_group.h's.
 //
 // NP = 16, 32 or 64 padded states, one NP-lane group per sequence, lane y =
 // state y, 64 / NP sequences per wave, kGroupWaves independent waves per block:

@@ -176,6 +176,11 @@ int check_var_lists(const std::string& what, const nipamd_model* mm, bool null, 
                     const std::string& bad_msg, int n_obs, const int* obs_vars, int n_query, const int* query);
 int chain_scope(const nipamd_model* mm, const std::string& what, const char* subject, const char* no_plan);
 bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int* qstride, int* qcard, int* width);
+// the verdicts soft evidence and the streams share, and the columns' roles (a: SoftArgs or StreamSoftArgs)
+template <typename A>
+int soft_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan, int n_obs,
+                 const int* obs_vars, int n_soft, const int* soft_vars, int n_query, const int* query, A& a, Route& r,
+                 int* width);
 bool chain_proper(const ChainPlan& P);
 bool estep16_sparse_ok(const ChainPlan& P, int ne);
 // the step-shrink bound (engine_route.cpp): kernels that rescale every 4th
@@ -222,6 +227,18 @@ void for_each_child(const ChainPlan& P, const Route& r, int ne, F f) {
   }
 }
 
+// run(d_lik) with the likelihood vectors lik [nli] on the device around it (a host-buffer call's)
+template <typename Run>
+int with_lik(const double* lik, size_t nli, Run run) {
+  DevBufs db;
+  double* d_lik = nullptr;
+  if (int rc = db.alloc(&d_lik, nli)) return rc;
+  if (nli) HIP_OK(hipMemcpy(d_lik, lik, nli * sizeof(double), hipMemcpyHostToDevice));
+  const int rc = run(d_lik);
+  if (rc == 0) HIP_OK(hipDeviceSynchronize());           // d_lik is freed on return
+  return rc;
+}
+
 // ---- the views and evidence columns of the kernels' argument structs
 // (chain_kernels.h: the fields are same-named across the structs)
 template <typename A>
@@ -235,12 +252,14 @@ template <typename A>
 void set_post_view(A& a, double* dst, long bstride, int tstride, int off) {
   a.post = dst; a.post_bstride = bstride; a.post_tstride = tstride; a.post_off = off;
 }
-// one [(M+2)][64] table pointer per observed column, and ebase
+// one [(M+2)][64] table pointer per observed column, and ebase; the columns
+// from nhard on are soft and keep their col (a.col[nhard..] must hold what soft_columns filled)
+constexpr int kAllHard = 4;   // the columns of Route::col
 template <typename A>
-void set_cols(A& a, const ChainPlan& P, const Route& r, const ReqTables& rt) {
+void set_cols(A& a, const ChainPlan& P, const Route& r, const ReqTables& rt, int nhard = kAllHard) {
   a.ncol = r.ncol;
   for (int i = 0; i < r.ncol; i++) {
-    a.col[i] = r.col[i];
+    if (i < nhard) a.col[i] = r.col[i];
     a.M[i] = P.emit(r.emit[i]).M;
     a.tab[i] = rt.tabw + rt.tabw_off[i];
   }

@@ -106,6 +106,59 @@ bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int
   return true;
 }
 
+// What soft_check and stream_check decide after check_var_lists, in this order:
+// the soft variables, chain_scope (subject, no_plan), a variable both hard and
+// soft, the route of the hard columns followed by the soft ones, the query.
+// Fills r and of a: N, ncol, nhard, M, col (a soft column's: where its weights
+// start in a row of lik), lik_tstride, the query digits, post_tstride = *width.
+template <typename A>
+int soft_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan, int n_obs,
+                 const int* obs_vars, int n_soft, const int* soft_vars, int n_query, const int* query, A& a, Route& r,
+                 int* width) {
+  for (int i = 0; i < n_soft; i++)
+    if (soft_vars[i] < 0 || soft_vars[i] >= (int)mm->m.vars.size())
+      return fail(NIP_ERROR_INVALID_ARGUMENT, what + ": bad soft-evidence variable");
+  if (int rc = chain_scope(mm, what, subject, no_plan)) return rc;
+  const auto& P = mm->m.chain;
+  std::vector<int> all(obs_vars, obs_vars + n_obs);
+  all.insert(all.end(), soft_vars, soft_vars + n_soft);
+  for (int i = 0; i < n_obs; i++)
+    for (int j = 0; j < n_soft; j++)
+      if (obs_vars[i] == soft_vars[j])
+        return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": a variable is listed as hard and as soft evidence");
+  std::string why;
+  if (!route_request(mm, (int)all.size(), all.data(), 0, nullptr, r, why))
+    return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": " + why);
+  bool is_if = n_query >= 1;
+  if (!P.joint) {
+    is_if = n_query == 1 && query[0] == P.v_cur;
+    a.nq = 0;
+    *width = P.N;
+  } else {
+    is_if = is_if && n_query <= nipamd::kViterbiMaxQuery &&
+            interface_digits(mm, n_query, query, a.qstride, a.qcard, width);
+    a.nq = n_query;
+  }
+  if (!is_if)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": the query is not a non-empty list of distinct current-slice "
+                                              "interface variables (at most " +
+                                              std::to_string(nipamd::kViterbiMaxQuery) + ")");
+  a.N = P.N;
+  a.ncol = r.ncol; a.nhard = n_obs;
+  a.lik_tstride = 0;
+  for (int i = 0; i < r.ncol; i++) {
+    a.M[i] = P.emit(r.emit[i]).M;
+    a.col[i] = r.col[i];
+    if (i >= n_obs) { a.col[i] = a.lik_tstride; a.lik_tstride += a.M[i]; }
+  }
+  a.post_tstride = *width;
+  return 0;
+}
+template int soft_columns(const std::string&, nipamd_model*, const char*, const char*, int, const int*, int, const int*,
+                          int, const int*, nipamd::SoftArgs&, Route&, int*);
+template int soft_columns(const std::string&, nipamd_model*, const char*, const char*, int, const int*, int, const int*,
+                          int, const int*, nipamd::StreamSoftArgs&, Route&, int*);
+
 // The chain's transition rows and every child's rows sum to 1 within 1e-15
 // (normalised CPTs; every m_step's output): the reference's per-step
 // log m2 - log m1 then telescope to log P(obs) (m1_t is the previous step's

@@ -4,8 +4,6 @@
 // soft ones (likelihood vectors); the chain plan routes them together and the
 // model's tables are looked up per call, as every entry point does
 // (engine_internal.h).
-#include <algorithm>
-
 #include "engine_internal.h"
 
 using namespace nipamd::eng;
@@ -15,7 +13,8 @@ namespace {
 static_assert(NIPAMD_STATUS_BAD_EVIDENCE == nipamd::kSoftBadEvidence, "include/nip_amd.h and chain_kernels.h disagree");
 
 // The verdict on a request -- the arguments, then the scope -- decided on the
-// host before anything touches the device (as stream_check and mlss_check).
+// host before anything touches the device (as stream_check and mlss_check;
+// soft_columns holds what stream_check decides likewise).
 // obs / lik / post: the caller's buffers (device or host), only tested for
 // NULL.  Fills the route, the shape, the columns' roles and the query digits
 // of a, and the rows' width.
@@ -27,49 +26,12 @@ int soft_check(const char* what, nipamd_model* mm, const void* obs, int n_obs, c
                                B < 1 || T < 1 || n_soft < 0, "bad arguments (B >= 1, T >= 1)", n_obs, obs_vars, n_query,
                                query))
     return rc;
-  for (int i = 0; i < n_soft; i++)
-    if (soft_vars[i] < 0 || soft_vars[i] >= (int)mm->m.vars.size())
-      return fail(NIP_ERROR_INVALID_ARGUMENT, std::string(what) + ": bad soft-evidence variable");
-  if (int rc = chain_scope(mm, what, "soft evidence",
-                           "the operator chain and the general engine take hard evidence only; "))
+  if (int rc = soft_columns(what, mm, "soft evidence",
+                            "the operator chain and the general engine take hard evidence only; ", n_obs, obs_vars,
+                            n_soft, soft_vars, n_query, query, a, r, width))
     return rc;
-  const auto& P = mm->m.chain;
-  // the hard columns, then the soft ones: one evidence list for the plan
-  std::vector<int> all(obs_vars, obs_vars + n_obs);
-  all.insert(all.end(), soft_vars, soft_vars + n_soft);
-  for (int i = 0; i < n_obs; i++)
-    for (int j = 0; j < n_soft; j++)
-      if (obs_vars[i] == soft_vars[j])
-        return fail(NIPAMD_ERROR_UNSUPPORTED, std::string(what) + ": a variable is listed as hard and as soft evidence");
-  std::string why;
-  if (!route_request(mm, (int)all.size(), all.data(), 0, nullptr, r, why))
-    return fail(NIPAMD_ERROR_UNSUPPORTED, std::string(what) + ": " + why);
-  // the query: distinct current-slice interface variables, at least one
-  bool is_if = n_query >= 1;
-  if (!P.joint) {
-    is_if = n_query == 1 && query[0] == P.v_cur;
-    a.nq = 0;
-    *width = P.N;
-  } else {
-    is_if = is_if && n_query <= nipamd::kViterbiMaxQuery &&
-            interface_digits(mm, n_query, query, a.qstride, a.qcard, width);
-    a.nq = n_query;
-  }
-  if (!is_if)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, std::string(what) + ": the query is not a non-empty list of distinct "
-                                              "current-slice interface variables (at most " +
-                                              std::to_string(nipamd::kViterbiMaxQuery) + ")");
-  a.B = B; a.T = T; a.N = P.N;
-  a.ncol = r.ncol; a.nhard = n_obs;
-  int W = 0;
-  for (int i = 0; i < r.ncol; i++) {
-    a.M[i] = P.emit(r.emit[i]).M;
-    a.col[i] = r.col[i];
-    if (i >= n_obs) { a.col[i] = W; W += a.M[i]; }         // a soft column: where its weights start in a row
-  }
-  a.lik_tstride = W;
-  a.lik_bstride = (long)T * W;
-  a.post_tstride = *width;
+  a.B = B; a.T = T;
+  a.lik_bstride = (long)T * a.lik_tstride;
   a.post_bstride = (long)T * *width;
   const int rc = nipamd::chain_soft_prepare(a);
   if (rc == nipamd::kLaunchRefused)
@@ -97,10 +59,7 @@ int soft_impl(const char* what, nipamd_model* mm, const int32_t* d_obs, int n_ob
   if (!filt)
     if (int rc = ensure_scratch(mm, nipamd::chain_soft_scratch_bytes(P.N, B, T))) return rc;
   const DevState* d = dev_of(mm);
-  int col[4];
-  std::copy(a.col, a.col + 4, col);
-  set_cols(a, P, r, *rt);
-  std::copy(col, col + 4, a.col);                        // the soft columns' offsets (soft_check)
+  set_cols(a, P, r, *rt, n_obs);
   set_obs_view(a, n_obs > 0 ? d_obs : nullptr, n_obs, T);
   a.lik = n_soft > 0 ? d_lik : nullptr;
   a.A = d->A64; a.sall = d->sall64; a.pi = d->pi64;
@@ -131,14 +90,10 @@ int soft_host_impl(const char* what, nipamd_model* mm, const int32_t* obs, int n
   const size_t nli = (size_t)B * T * W;
   return host_call(n_obs > 0 ? obs : nullptr, nob, post, npo, false, ll, status, (size_t)B,
                    [&](int32_t* d_obs, double* d_post, double* d_ll, uint32_t* d_st) {
-                     DevBufs db;
-                     double* d_lik = nullptr;
-                     if (int rc = db.alloc(&d_lik, nli)) return rc;
-                     if (nli) HIP_OK(hipMemcpy(d_lik, lik, nli * sizeof(double), hipMemcpyHostToDevice));
-                     const int rc = soft_impl(what, mm, d_obs, n_obs, obs_vars, d_lik, n_soft, soft_vars, B, T, n_query,
-                                              query, d_post, d_ll, d_st, nullptr, filt);
-                     if (rc == 0) HIP_OK(hipDeviceSynchronize());   // d_lik is freed on return
-                     return rc;
+                     return with_lik(lik, nli, [&](const double* d_lik) {
+                       return soft_impl(what, mm, d_obs, n_obs, obs_vars, d_lik, n_soft, soft_vars, B, T, n_query, query,
+                                        d_post, d_ll, d_st, nullptr, filt);
+                     });
                    });
 }
 

@@ -32,9 +32,9 @@ static_assert(NIPAMD_STREAM_CHUNK == nipamd::kStreamChunk && NIPAMD_STREAM_MAX_L
               "include/nip_amd.h and chain_kernels.h disagree");
 
 // The verdict on a stream -- the arguments, then the scope -- decided on the
-// host before anything touches the device (as mlss_check; with soft columns
-// the union of this verdict and soft_check's).  Fills the route, the columns'
-// roles, the query digits and the shape of s.
+// host before anything touches the device (as mlss_check; soft_columns holds
+// what soft_check decides likewise).  Fills the route, the columns' roles, the
+// query digits and the shape of s.
 int stream_check(nipamd_model* mm, int n_obs, const int* obs_vars, int n_soft, const int* soft_vars, int n_query,
                  const int* query, int B, int lag, nipamd_stream** out, nipamd_stream& s) {
   if (int rc = check_var_lists("stream", mm, !out || (n_soft > 0 && !soft_vars), "NULL model, variables or result",
@@ -42,49 +42,13 @@ int stream_check(nipamd_model* mm, int n_obs, const int* obs_vars, int n_soft, c
                                "bad arguments (B >= 1, 0 <= lag <= " + std::to_string(NIPAMD_STREAM_MAX_LAG) + ")",
                                n_obs, obs_vars, n_query, query))
     return rc;
-  for (int i = 0; i < n_soft; i++)
-    if (soft_vars[i] < 0 || soft_vars[i] >= (int)mm->m.vars.size())
-      return fail(NIP_ERROR_INVALID_ARGUMENT, "stream: bad soft-evidence variable");
-  if (int rc = chain_scope(mm, "stream", "online inference",
-                           "the operator chain and the general engine have no online form; "))
-    return rc;
-  const auto& P = mm->m.chain;
-  // the hard columns, then the soft ones: one evidence list for the plan
-  std::vector<int> all(obs_vars, obs_vars + n_obs);
-  all.insert(all.end(), soft_vars, soft_vars + n_soft);
-  for (int i = 0; i < n_obs; i++)
-    for (int j = 0; j < n_soft; j++)
-      if (obs_vars[i] == soft_vars[j])
-        return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: a variable is listed as hard and as soft evidence");
-  std::string why;
-  if (!route_request(mm, (int)all.size(), all.data(), 0, nullptr, s.r, why))
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: " + why);
-  // the query: distinct current-slice interface variables, at least one
   nipamd::StreamSoftArgs& a = s.a;
-  bool is_if = n_query >= 1;
-  if (!P.joint) {
-    is_if = n_query == 1 && query[0] == P.v_cur;
-    a.nq = 0;
-    s.width = P.N;
-  } else {
-    is_if = is_if && n_query <= nipamd::kViterbiMaxQuery &&
-            interface_digits(mm, n_query, query, a.qstride, a.qcard, &s.width);
-    a.nq = n_query;
-  }
-  if (!is_if)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "stream: the query is not a non-empty list of distinct current-slice "
-                                          "interface variables (at most " +
-                                              std::to_string(nipamd::kViterbiMaxQuery) + ")");
-  a.B = B; a.N = P.N; a.lag = lag;
-  a.ncol = s.r.ncol; a.nhard = n_obs;
-  s.W = 0;
-  for (int i = 0; i < s.r.ncol; i++) {
-    a.M[i] = P.emit(s.r.emit[i]).M;
-    a.col[i] = s.r.col[i];
-    if (i >= n_obs) { a.col[i] = s.W; s.W += a.M[i]; }     // a soft column: where its weights start in a row
-  }
-  a.lik_tstride = s.W;
-  a.post_tstride = s.width;
+  if (int rc = soft_columns("stream", mm, "online inference",
+                            "the operator chain and the general engine have no online form; ", n_obs, obs_vars,
+                            n_soft, soft_vars, n_query, query, a, s.r, &s.width))
+    return rc;
+  a.B = B; a.lag = lag;
+  s.W = a.lik_tstride;
   if (n_soft > 0) {
     const int rc = nipamd::chain_stream_soft_prepare(a);
     if (rc == nipamd::kLaunchRefused)
@@ -115,8 +79,7 @@ int stream_tables(nipamd_stream* s, Args& a) {
   ReqTables* rt = nullptr;
   if (int rc = ensure_req_tables(mm, s->r, &rt)) return rc;
   const DevState* d = dev_of(mm);
-  set_cols(a, mm->m.chain, s->r, *rt);
-  std::copy(s->a.col, s->a.col + 4, a.col);            // the soft columns' offsets (stream_check)
+  set_cols(a, mm->m.chain, s->r, *rt, (int)s->obs_vars.size());
   a.A = d->A64; a.sall = d->sall64;
   return 0;
 }
@@ -286,13 +249,9 @@ int nipamd_stream_push_soft_host(nipamd_stream* s, const int32_t* obs, const dou
   const size_t nli = (size_t)s->B * T * (size_t)s->W;
   return host_call(s->obs_vars.empty() ? nullptr : obs, nob, npo ? post : nullptr, npo, false, ll, status, (size_t)s->B,
                    [&](int32_t* d_obs, double* d_post, double* d_ll, uint32_t* d_st) {
-                     DevBufs db;
-                     double* d_lik = nullptr;
-                     if (int rc = db.alloc(&d_lik, nli)) return rc;
-                     if (nli) HIP_OK(hipMemcpy(d_lik, lik, nli * sizeof(double), hipMemcpyHostToDevice));
-                     const int rc = stream_run(s, d_obs, d_lik, T, d_post, d_ll, d_st, nullptr);
-                     if (rc == 0) HIP_OK(hipDeviceSynchronize());   // d_lik is freed on return
-                     return rc;
+                     return with_lik(lik, nli, [&](const double* d_lik) {
+                       return stream_run(s, d_obs, d_lik, T, d_post, d_ll, d_st, nullptr);
+                     });
                    });
 }
 

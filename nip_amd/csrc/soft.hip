@@ -13,7 +13,7 @@
 // scaling a step's vector by c adds log c to the ll and moves no row, for any
 // finite non-negative vector with a positive entry (denormals to DBL_MAX): a
 // vector is used at the scale of its largest weight and the power of two taken
-// out goes to the ll's exponent (evid below), so e_t is a product of factors of
+// out goes to the ll's exponent (soft_evid), so e_t is a product of factors of
 // ordinary size.  Everything else is stream.hip's recursion on a whole sequence
 // (DESIGN.md 2):
 //
@@ -43,13 +43,11 @@
 // their use (their first NP; a longer vector's remaining pieces on demand), put
 // into the wave's own LDS row and summed by every lane in the order of o.  A
 // sequence's results depend on its own inputs alone, bit for bit: every
-// cross-lane operation stays inside the group.
+// cross-lane operation stays inside the group.  The step's loads and evidence, the
+// rows, the backward step and the ladder: soft_group.h, with the stream kernels.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
-
-#include "chain_group.h"
-#include "store_pol.h"
+#include "soft_group.h"
 
 namespace nipamd {
 
@@ -61,11 +59,11 @@ namespace {
 template <int NP, int NC, int NH, bool LONG>
 __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a) {
   static_assert(NH >= 0 && NH <= NC, "the hard columns are the first of the columns");
-  constexpr int G = 64 / NP;
   constexpr int NCA = NC > 0 ? NC : 1;
+  constexpr int G = 64 / NP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [rows][NP] tables, ebase [NP], A and A^T [NP][NP] (NP > 16), [waves][64] exchange rows,
-  // [waves][64] weight rows
+  // [waves][64] weight rows (staging and lane geometry stay written out: soft_group.h says why)
   double* tabs = reinterpret_cast<double*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int row0[NCA];
@@ -91,7 +89,6 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
   const bool live = b < a.B;
   const long bl = live ? b : a.B - 1;
   const int T = a.T;
-
   double Ac[16], Ar[16];                                   // column y and row y of A (NP = 16)
   if constexpr (NP == 16) {
 #pragma unroll
@@ -105,115 +102,19 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
   }
   const double sall = a.sall[y];
 
-  // what a step reads from memory: the hard columns' codes, and this lane's
-  // weight of the first NP of every soft column (past the vector's end: its first weight again, unused)
-  struct Step {
-    int code[NCA];
-    double w[NCA];
-  };
-  const int* orow = a.obs + bl * a.obs_bstride;            // dereferenced with NH > 0 only
-  const double* lrow = a.lik + bl * a.lik_bstride;         // dereferenced with NH < NC only
-  auto fetch = [&](int t, Step& s) {
-#pragma unroll
-    for (int k = 0; k < NC; k++) {
-      s.code[k] = 0;
-      s.w[k] = 0.0;
-      if (k < NH) s.code[k] = orow[(long)t * a.obs_tstride + a.col[k]];
-      else s.w[k] = lrow[(long)t * a.lik_tstride + a.col[k] + (y < a.M[k] ? y : 0)];
-    }
-  };
-  // e_t of this lane's state from the step's loads, every soft vector taken at
-  // the scale of its largest weight: w 2^-ex with 2^(ex-1) <= max w < 2^ex
-  // (frexp / ldexp: exact), so that a column's sum is of the size of its table's
-  // entries whatever the caller's scale, the product over the columns neither
-  // overflows nor underflows on the way, and the rows are the same bits for w
-  // and for 2^k w.  exs: the sum of the columns' ex, which the forward pass adds
-  // to the ll's exponent (the backward pass normalises and needs none).  bad: a
-  // weight of the group's sequence is negative, NaN or infinite (then e_t = 0);
-  // such a weight is 0 before the maximum is taken.
+  using Step = SoftStep<NCA>;
+  const int* orow = a.obs + bl * a.obs_bstride;
+  const double* lrow = a.lik + bl * a.lik_bstride;
+  auto fetch = [&](int t, Step& s) { soft_fetch<NP, NC, NH>(a, orow, lrow, y, t, s); };
   auto evid = [&](int t, const Step& s, bool& bad, long& exs) {
-    double e = eb[y];
-    bool mine = false;
-    exs = 0;
-#pragma unroll
-    for (int k = 0; k < NC; k++) {
-      if (k < NH) {
-        e *= tabs[(row0[k] + code_of(s.code[k], a.M[k])) * NP + y];
-      } else {
-        const int M = a.M[k];
-        const double* tk = tabs + row0[k] * NP + y;
-        // this lane's weight of the piece from c0 on, a bad one as 0 (past the
-        // vector's end: its first weight again, which cannot raise the maximum)
-        auto valid = [&](double w, int c0) {
-          const bool wb = !(w >= 0.0 && w <= DBL_MAX);
-          mine |= wb && c0 + y < M;
-          return wb ? 0.0 : w;
-        };
-        auto later = [&](int c0) {
-          return lrow[(long)t * a.lik_tstride + a.col[k] + (c0 + y < M ? c0 + y : 0)];
-        };
-        const double w0 = valid(s.w[k], 0);
-        double mx = w0;
-        if constexpr (LONG)
-          for (int c0 = NP; c0 < M; c0 += NP) mx = fmax(mx, valid(later(c0), c0));
-        int ex = 0;
-        (void)frexp(group_max<NP>(mx), &ex);               // 0 for a maximum of 0
-        exs += ex;
-        double acc = 0.0;
-        // the weights o = c0 .. c0 + n - 1, this lane's being w
-        auto piece = [&](double w, int c0) {
-          wrow[lane] = ldexp(w, -ex);
-          wave_lds_sync();
-          const int n = M - c0 < NP ? M - c0 : NP;
-          for (int o = 0; o < n; o++) acc = fma(wrow[gbase + o], tk[(c0 + o) * NP], acc);
-          wave_lds_sync();
-        };
-        piece(w0, 0);
-        if constexpr (LONG)
-          for (int c0 = NP; c0 < M; c0 += NP) piece(valid(later(c0), c0), c0);
-        e *= acc;
-      }
-    }
-    constexpr unsigned long long gmask = NP == 64 ? ~0ull : (1ull << (NP & 63)) - 1ull;
-    bad = ((__ballot(mine) >> gbase) & gmask) != 0ull;
-    return bad ? 0.0 : e;
+    return soft_evid<NP, NC, NH, LONG>(a, tabs, eb, row0, wrow, lrow, lane, gbase, y, t, s, bad, exs);
   };
-
+  // A row's values (row_value) and its store are two steps: the store of row r
+  // is issued one loop iteration late, right after the next step's loads, so
+  // that a wait for those loads never waits for a store just issued.
   const int width = a.post_tstride;
   double* prow = a.post + bl * a.post_bstride;
-  // A row's values and its store are two steps: the store of row r is issued
-  // one loop iteration late, right after the next step's loads, so that a wait
-  // for those loads never waits for a store just issued.
-  // value: normalise(p) (norm; else p as it is: alpha^ is normalised), all
-  // zeros for a sequence without mass
-  auto value = [&](double p, bool norm, bool zero) {
-    double v = p;
-    if (norm) {
-      const double s = group_sum<NP>(p);
-      v = s > 0.0 ? p / s : 0.0;
-    }
-    return zero ? 0.0 : v;
-  };
-  // row r from its values: the interface state itself, or the queried
-  // variables' digit sums (as chain_stream_kernel's rows)
-  auto put = [&](double v, int r) {
-    double* dst = prow + (long)r * width;
-    if (a.nq == 0) {
-      if (live && y < a.N) store_pol<NIPAMD_POST_NT != 0>(dst + y, v);
-      return;
-    }
-    xch[lane] = v;
-    wave_lds_sync();
-    for (int c = y; c < width; c += NP) {
-      int j = 0, d = c;
-      while (j < a.nq - 1 && d >= a.qcard[j]) { d -= a.qcard[j]; j++; }
-      const int qs = a.qstride[j], qc = a.qcard[j];
-      double acc = 0.0;
-      for (int x = 0; x < a.N; x++) acc += (x / qs) % qc == d ? xch[gbase + x] : 0.0;
-      if (live) store_pol<NIPAMD_POST_NT != 0>(dst + c, acc);
-    }
-    wave_lds_sync();
-  };
+  auto put = [&](double v, int r) { row_put<NP>(a, prow, width, xch, live, lane, gbase, y, v, r); };
 
   // forward: the steps' loads run one step ahead, the stores one step behind
   Totals tot{1.0, 1.0, 0, 0u, kStreamAlive};
@@ -236,7 +137,7 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
       hd = fwd_step<NP, true>(hd, e, sall, Ac, Af, xch, lane, gbase, y, t, tot);
       tot.ex += exs;                                       // m2 of the weights as given is 2^exs times fwd_step's
       if (bad) tot.status |= kSoftBadEvidence;
-      owed = decltype(filter)::value ? value(hd, false, tot.dead != kStreamAlive) : hd;
+      owed = decltype(filter)::value ? row_value<NP>(hd, false, tot.dead != kStreamAlive) : hd;
       cur = nxt;
     }
     store(T - 1);
@@ -244,16 +145,14 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
   if (a.filter) forward(std::true_type{});
   else forward(std::false_type{});
   if (live && y == 0) {
-    if (a.ll)
-      a.ll[b] = tot.dead != kStreamAlive ? -DBL_MAX
-                                         : log(tot.num) - log(tot.den) + (double)tot.ex * 0.69314718055994530942;
+    if (a.ll) a.ll[b] = totals_ll(tot);
     if (a.status) a.status[b] = tot.status;
   }
   if (a.filter) return;
 
   // backward: cur holds step T - 1; beta = 1 there
   const bool zero = tot.dead != kStreamAlive;
-  owed = value(hd, true, zero);
+  owed = row_value<NP>(hd, true, zero);
   double beta = 1.0;
   double al = T > 1 ? srow[(long)(T - 2) * NP] : 0.0;
   for (int t = T - 2; t >= 0; t--) {
@@ -262,12 +161,8 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_soft_kernel(SoftArgs a
     put(owed, t + 1);
     bool bad;
     long exs;
-    const double e = evid(t + 1, cur, bad, exs);
-    beta = matvec<NP>(e * beta, Ar, Ab, xch, lane, gbase, y);
-    int ex = 0;
-    (void)frexp(group_max<NP>(beta), &ex);                 // 0 for a maximum of 0
-    beta = ldexp(beta, -ex);
-    owed = value(al * beta, true, zero);
+    beta = bwd_step<NP>(evid(t + 1, cur, bad, exs), beta, Ar, Ab, xch, lane, gbase, y);
+    owed = row_value<NP>(al * beta, true, zero);
     cur = nxt;
     al = aln;
   }
@@ -279,23 +174,9 @@ bool soft_shape_ok(const SoftArgs& a) {
 }
 
 int soft_dispatch(const SoftArgs& a, bool launch, hipStream_t stream) {
-  // one group_launch per (NH, LONG): its dynamic-LDS bookkeeping is per kernel_of
-  auto variant = [&](auto nh, auto lng) {
-    return group_launch(a, chain_soft_lds_bytes(a), launch, stream, [](auto np, auto nc) {
-      constexpr int NC = decltype(nc)::value, NH = decltype(nh)::value < NC ? decltype(nh)::value : NC;
-      return &chain_soft_kernel<decltype(np)::value, NC, NH, decltype(lng)::value && NH < NC>;
-    });
-  };
-  bool lng = false;
-  for (int k = a.nhard; k < a.ncol; k++) lng |= a.M[k] > group_np(a.N);
-  auto hard = [&](auto nh) { return lng ? variant(nh, std::true_type{}) : variant(nh, std::false_type{}); };
-  switch (a.nhard) {
-    case 0: return hard(std::integral_constant<int, 0>{});
-    case 1: return hard(std::integral_constant<int, 1>{});
-    case 2: return hard(std::integral_constant<int, 2>{});
-    case 3: return hard(std::integral_constant<int, 3>{});
-    default: return hard(std::integral_constant<int, 4>{});
-  }
+  return soft_group_launch(a, launch, stream, [](auto np, auto nc, auto nh, auto lng) {
+    return &chain_soft_kernel<decltype(np)::value, decltype(nc)::value, decltype(nh)::value, decltype(lng)::value>;
+  });
 }
 
 }  // namespace
@@ -304,11 +185,7 @@ size_t chain_soft_scratch_bytes(int N, long B, int T) {
   return (size_t)B * (size_t)T * group_np(N) * sizeof(double);
 }
 
-size_t chain_soft_lds_bytes(const SoftArgs& a) {
-  const int NP = group_np(a.N);
-  const size_t dbl = evid_rows(a) * NP + (NP > 16 ? 2 * (size_t)NP * NP : 0) + 2 * kGroupWaves * 64;
-  return dbl * sizeof(double);
-}
+size_t chain_soft_lds_bytes(const SoftArgs& a) { return soft_lds_bytes(a); }
 
 int chain_soft_prepare(const SoftArgs& a) {
   if (!soft_shape_ok(a)) return kLaunchRefused;

@@ -35,18 +35,16 @@
 // they are bit-identical.
 //
 // Layout: chain_group.h's lane groups (NP = 16, 32 or 64 padded states, one
-// NP-lane group per sequence), no block barrier after the tables are staged.
+// NP-lane group per sequence), one block barrier after the tables are staged.
 // At NP = 16 column y and row y of A stay in registers and both mat-vecs are
 // dpp_row.h's dot_bcast; above that the operand goes through the wave's own
 // LDS row and A / A^T sit in LDS.  The evidence tables and the window's codes
 // (the pending ring, then the new steps), as table rows, are staged in LDS.
-// Every cross-lane sum starts from a materialised value (row_sum).
+// Every cross-lane sum starts from a materialised value (row_sum).  Rows, the
+// backward step and the state's write-back: soft_group.h, with the soft kernels.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
-
-#include "chain_group.h"
-#include "store_pol.h"
+#include "soft_group.h"
 
 namespace nipamd {
 
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_kernel(StreamAr
   constexpr int NCA = NC > 0 ? NC : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [rows][NP] tables, ebase [NP], A and A^T [NP][NP] (NP > 16), [waves][64] exchange rows,
-  // then the waves' codes [G][lag + kStreamChunk][NC] (int)
+  // then the waves' codes [G][lag + kStreamChunk][NC] (int); written out: soft_group.h says why
   double* tabs = reinterpret_cast<double*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int row0[NCA];
@@ -130,35 +128,9 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_kernel(StreamAr
   double hd = a.head[bl * NP + y];
   const int width = a.post_tstride;
   double* prow = a.post ? a.post + bl * a.post_bstride : nullptr;
-
-  // row = normalise(p) (norm; else p as it is: alpha^ is normalised), all zeros
-  // where the sequence has no mass at the row's endpoint; the interface state
-  // itself, or the queried variables' digit sums
   auto emit = [&](double p, bool norm, bool zero, int r) {
-    double v = p;
-    if (norm) {
-      const double s = group_sum<NP>(p);
-      v = s > 0.0 ? p / s : 0.0;
-    }
-    v = zero ? 0.0 : v;
-    double* dst = prow + (long)r * width;
-    if (a.nq == 0) {
-      if (live && y < a.N) store_pol<NIPAMD_POST_NT != 0>(dst + y, v);
-      return;
-    }
-    xch[lane] = v;
-    wave_lds_sync();
-    for (int c = y; c < width; c += NP) {
-      int j = 0, d = c;
-      while (j < a.nq - 1 && d >= a.qcard[j]) { d -= a.qcard[j]; j++; }
-      const int qs = a.qstride[j], qc = a.qcard[j];
-      double acc = 0.0;
-      for (int x = 0; x < a.N; x++) acc += (x / qs) % qc == d ? xch[gbase + x] : 0.0;
-      if (live) store_pol<NIPAMD_POST_NT != 0>(dst + c, acc);
-    }
-    wave_lds_sync();
+    row_put<NP>(a, prow, width, xch, live, lane, gbase, y, row_value<NP>(p, norm, zero), r);
   };
-
   if (L == 0) {
     // filtering: the row of step t is alpha^_t itself
     for (int w = 0; w < Tn; w++) {
@@ -173,33 +145,14 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_kernel(StreamAr
       bs = fwd_step<NP, false>(bs, evid(r), sall, Ac, Af, xch, lane, gbase, y, s0 + r, none);
       const int endw = a.final ? W - 1 : r + L;            // the row's endpoint min(t + L, n_end - 1)
       double beta = 1.0;
-      for (int j = endw; j > r; j--) {
-        beta = matvec<NP>(evid(j) * beta, Ar, Ab, xch, lane, gbase, y);
-        int ex = 0;
-        (void)frexp(group_max<NP>(beta), &ex);            // 0 for a maximum of 0
-        beta = ldexp(beta, -ex);
-      }
+      for (int j = endw; j > r; j--) beta = bwd_step<NP>(evid(j), beta, Ar, Ab, xch, lane, gbase, y);
       emit(bs * beta, true, s0 + endw >= tot.dead, r);
     }
     if (live) a.base[b * NP + y] = bs;
   }
 
   // the state, and the new steps that stay pending into the ring
-  if (live) {
-    a.head[b * NP + y] = hd;
-    if (y == 0) {
-      a.snum[b] = tot.num;
-      a.sden[b] = tot.den;
-      a.sexp[b] = tot.ex;
-      a.sstatus[b] = tot.status;
-      a.sdead[b] = tot.dead;
-      if (a.ll)
-        a.ll[b] = tot.dead != kStreamAlive
-                      ? -DBL_MAX
-                      : log(tot.num) - log(tot.den) + (double)tot.ex * 0.69314718055994530942;
-      if (a.status) a.status[b] = tot.status;
-    }
-  }
+  stream_state_store<NP>(a, b, live, y, hd, tot);
   if constexpr (NC > 0) {
     const long nend = a.n + Tn;
     const long keep = nend < L ? nend : L;                 // pending after this launch
@@ -248,10 +201,8 @@ int str_dispatch(const StreamArgs& a, bool launch, hipStream_t stream) {
 int chain_stream_np(int N) { return group_np(N); }
 
 size_t chain_stream_lds_bytes(const StreamArgs& a) {
-  const int NP = group_np(a.N), G = 64 / NP;
-  const size_t dbl = evid_rows(a) * NP + (NP > 16 ? 2 * (size_t)NP * NP : 0) + kGroupWaves * 64;
-  const size_t ints = (size_t)kGroupWaves * G * (a.lag + kStreamChunk) * a.ncol;
-  return dbl * sizeof(double) + ints * sizeof(int);
+  const size_t ints = (size_t)kGroupWaves * (64 / group_np(a.N)) * (a.lag + kStreamChunk) * a.ncol;
+  return group_lds_doubles(a, a.N, 1) * sizeof(double) + ints * sizeof(int);
 }
 
 int chain_stream_prepare(const StreamArgs& a) {

@@ -44,16 +44,12 @@
 // The new steps' codes and weights are loaded one step ahead of their use, the
 // base's e_t too, and the ring's e_j of the backward recursion in blocks of
 // four, a block ahead: their addresses do not depend on the recursion, and a
-// backward step is too short to cover a load from L2 by itself.  evid below is soft.hip's
-// and emit stream.hip's, written out again: both close over their kernel's
-// locals, and the two kernels that have them keep the code and the bits they
-// have.
+// backward step is too short to cover a load from L2 by itself.  The step's
+// loads and evidence are soft.hip's and the rows, the backward step and the
+// state's write-back stream.hip's: one definition each, in soft_group.h.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
-
-#include "chain_group.h"
-#include "store_pol.h"
+#include "soft_group.h"
 
 namespace nipamd {
 
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_soft_kernel(Str
   constexpr int kAhead = 4;                                // the backward pass's e_j are loaded in blocks of four
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [rows][NP] tables, ebase [NP], A and A^T [NP][NP] (NP > 16), [waves][64] exchange rows,
-  // [waves][64] weight rows
+  // [waves][64] weight rows (staging and lane geometry stay written out: soft_group.h says why)
   double* tabs = reinterpret_cast<double*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int row0[NCA];
@@ -98,7 +94,6 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_soft_kernel(Str
   const int L = a.lag, P = a.pending, Tn = a.T_new, W = P + Tn;
   const int R = L + kStreamChunk;                          // the ring's slots (L > 0)
   const long s0 = a.n - P;                                 // the step of window index 0
-
   double Ac[16], Ar[16];                                   // column y and row y of A (NP = 16)
   if constexpr (NP == 16) {
 #pragma unroll
@@ -112,75 +107,12 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_soft_kernel(Str
   }
   const double sall = a.sall[y];
 
-  // what a new step reads from memory: the hard columns' codes, and this lane's
-  // weight of the first NP of every soft column (past the vector's end: its first weight again, unused)
-  struct Step {
-    int code[NCA];
-    double w[NCA];
-  };
-  const int* orow = a.obs + bl * a.obs_bstride;            // dereferenced with NH > 0 only
-  const double* lrow = a.lik + bl * a.lik_bstride;         // dereferenced with NH < NC only
-  auto fetch = [&](int t, Step& s) {                       // t: among the launch's new steps
-#pragma unroll
-    for (int k = 0; k < NC; k++) {
-      s.code[k] = 0;
-      s.w[k] = 0.0;
-      if (k < NH) s.code[k] = orow[(long)t * a.obs_tstride + a.col[k]];
-      else s.w[k] = lrow[(long)t * a.lik_tstride + a.col[k] + (y < a.M[k] ? y : 0)];
-    }
-  };
-  // e_t of this lane's state from the step's loads, every soft vector taken at
-  // the scale of its largest weight: w 2^-ex with 2^(ex-1) <= max w < 2^ex
-  // (frexp / ldexp: exact).  exs: the sum of the columns' ex, which the head
-  // adds to the ll's exponent.  bad: a weight of the group's sequence is
-  // negative, NaN or infinite (then e_t = 0); such a weight is 0 before the
-  // maximum is taken.  (chain_soft_kernel's evid.)
+  using Step = SoftStep<NCA>;                              // of new step t, t among the launch's
+  const int* orow = a.obs + bl * a.obs_bstride;
+  const double* lrow = a.lik + bl * a.lik_bstride;
+  auto fetch = [&](int t, Step& s) { soft_fetch<NP, NC, NH>(a, orow, lrow, y, t, s); };
   auto evid = [&](int t, const Step& s, bool& bad, long& exs) {
-    double e = eb[y];
-    bool mine = false;
-    exs = 0;
-#pragma unroll
-    for (int k = 0; k < NC; k++) {
-      if (k < NH) {
-        e *= tabs[(row0[k] + code_of(s.code[k], a.M[k])) * NP + y];
-      } else {
-        const int M = a.M[k];
-        const double* tk = tabs + row0[k] * NP + y;
-        // this lane's weight of the piece from c0 on, a bad one as 0 (past the
-        // vector's end: its first weight again, which cannot raise the maximum)
-        auto valid = [&](double w, int c0) {
-          const bool wb = !(w >= 0.0 && w <= DBL_MAX);
-          mine |= wb && c0 + y < M;
-          return wb ? 0.0 : w;
-        };
-        auto later = [&](int c0) {
-          return lrow[(long)t * a.lik_tstride + a.col[k] + (c0 + y < M ? c0 + y : 0)];
-        };
-        const double w0 = valid(s.w[k], 0);
-        double mx = w0;
-        if constexpr (LONG)
-          for (int c0 = NP; c0 < M; c0 += NP) mx = fmax(mx, valid(later(c0), c0));
-        int ex = 0;
-        (void)frexp(group_max<NP>(mx), &ex);               // 0 for a maximum of 0
-        exs += ex;
-        double acc = 0.0;
-        // the weights o = c0 .. c0 + n - 1, this lane's being w
-        auto piece = [&](double w, int c0) {
-          wrow[lane] = ldexp(w, -ex);
-          wave_lds_sync();
-          const int n = M - c0 < NP ? M - c0 : NP;
-          for (int o = 0; o < n; o++) acc = fma(wrow[gbase + o], tk[(c0 + o) * NP], acc);
-          wave_lds_sync();
-        };
-        piece(w0, 0);
-        if constexpr (LONG)
-          for (int c0 = NP; c0 < M; c0 += NP) piece(valid(later(c0), c0), c0);
-        e *= acc;
-      }
-    }
-    constexpr unsigned long long gmask = NP == 64 ? ~0ull : (1ull << (NP & 63)) - 1ull;
-    bad = ((__ballot(mine) >> gbase) & gmask) != 0ull;
-    return bad ? 0.0 : e;
+    return soft_evid<NP, NC, NH, LONG>(a, tabs, eb, row0, wrow, lrow, lane, gbase, y, t, s, bad, exs);
   };
 
   Totals tot{a.snum[bl], a.sden[bl], a.sexp[bl], a.sstatus[bl], a.sdead[bl]};
@@ -188,33 +120,8 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_soft_kernel(Str
   double hd = a.head[bl * NP + y];
   const int width = a.post_tstride;
   double* prow = a.post ? a.post + bl * a.post_bstride : nullptr;
-
-  // row = normalise(p) (norm; else p as it is: alpha^ is normalised), all zeros
-  // where the sequence has no mass at the row's endpoint; the interface state
-  // itself, or the queried variables' digit sums (chain_stream_kernel's emit)
   auto emit = [&](double p, bool norm, bool zero, int r) {
-    double v = p;
-    if (norm) {
-      const double s = group_sum<NP>(p);
-      v = s > 0.0 ? p / s : 0.0;
-    }
-    v = zero ? 0.0 : v;
-    double* dst = prow + (long)r * width;
-    if (a.nq == 0) {
-      if (live && y < a.N) store_pol<NIPAMD_POST_NT != 0>(dst + y, v);
-      return;
-    }
-    xch[lane] = v;
-    wave_lds_sync();
-    for (int c = y; c < width; c += NP) {
-      int j = 0, d = c;
-      while (j < a.nq - 1 && d >= a.qcard[j]) { d -= a.qcard[j]; j++; }
-      const int qs = a.qstride[j], qc = a.qcard[j];
-      double acc = 0.0;
-      for (int x = 0; x < a.N; x++) acc += (x / qs) % qc == d ? xch[gbase + x] : 0.0;
-      if (live) store_pol<NIPAMD_POST_NT != 0>(dst + c, acc);
-    }
-    wave_lds_sync();
+    row_put<NP>(a, prow, width, xch, live, lane, gbase, y, row_value<NP>(p, norm, zero), r);
   };
 
   // this lane's e of window index w (step s0 + w) in the ring
@@ -255,12 +162,7 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_soft_kernel(Str
       double e0 = back(endw), e1 = back(endw - 1), e2 = back(endw - 2), e3 = back(endw - 3);
       bs = fwd_step<NP, false>(bs, er, sall, Ac, Af, xch, lane, gbase, y, s0 + r, none);
       double beta = 1.0;
-      auto bwd = [&](double e) {
-        beta = matvec<NP>(e * beta, Ar, Ab, xch, lane, gbase, y);
-        int ex = 0;
-        (void)frexp(group_max<NP>(beta), &ex);            // 0 for a maximum of 0
-        beta = ldexp(beta, -ex);
-      };
+      auto bwd = [&](double e) { beta = bwd_step<NP>(e, beta, Ar, Ab, xch, lane, gbase, y); };
       int j = endw;
       for (; j - r >= kAhead; j -= kAhead) {
         const double c0 = e0, c1 = e1, c2 = e2, c3 = e3;
@@ -278,22 +180,7 @@ __global__ __launch_bounds__(kGroupWaves * 64) void chain_stream_soft_kernel(Str
     if (live) a.base[b * NP + y] = bs;
   }
 
-  // the state (the new steps' e_t are in the ring already)
-  if (live) {
-    a.head[b * NP + y] = hd;
-    if (y == 0) {
-      a.snum[b] = tot.num;
-      a.sden[b] = tot.den;
-      a.sexp[b] = tot.ex;
-      a.sstatus[b] = tot.status;
-      a.sdead[b] = tot.dead;
-      if (a.ll)
-        a.ll[b] = tot.dead != kStreamAlive
-                      ? -DBL_MAX
-                      : log(tot.num) - log(tot.den) + (double)tot.ex * 0.69314718055994530942;
-      if (a.status) a.status[b] = tot.status;
-    }
-  }
+  stream_state_store<NP>(a, b, live, y, hd, tot);                   // (the new steps' e_t are in the ring already)
 }
 
 bool sstr_shape_ok(const StreamSoftArgs& a) {
@@ -301,32 +188,15 @@ bool sstr_shape_ok(const StreamSoftArgs& a) {
 }
 
 int sstr_dispatch(const StreamSoftArgs& a, bool launch, hipStream_t stream) {
-  // one group_launch per (NH, LONG): its dynamic-LDS bookkeeping is per kernel_of
-  auto variant = [&](auto nh, auto lng) {
-    return group_launch(a, chain_stream_soft_lds_bytes(a), launch, stream, [](auto np, auto nc) {
-      constexpr int NC = decltype(nc)::value, NH = decltype(nh)::value < NC ? decltype(nh)::value : NC;
-      return &chain_stream_soft_kernel<decltype(np)::value, NC, NH, decltype(lng)::value && NH < NC>;
-    });
-  };
-  bool lng = false;
-  for (int k = a.nhard; k < a.ncol; k++) lng |= a.M[k] > group_np(a.N);
-  auto hard = [&](auto nh) { return lng ? variant(nh, std::true_type{}) : variant(nh, std::false_type{}); };
-  switch (a.nhard) {
-    case 0: return hard(std::integral_constant<int, 0>{});
-    case 1: return hard(std::integral_constant<int, 1>{});
-    case 2: return hard(std::integral_constant<int, 2>{});
-    case 3: return hard(std::integral_constant<int, 3>{});
-    default: return hard(std::integral_constant<int, 4>{});
-  }
+  return soft_group_launch(a, launch, stream, [](auto np, auto nc, auto nh, auto lng) {
+    return &chain_stream_soft_kernel<decltype(np)::value, decltype(nc)::value, decltype(nh)::value,
+                                     decltype(lng)::value>;
+  });
 }
 
 }  // namespace
 
-size_t chain_stream_soft_lds_bytes(const StreamSoftArgs& a) {
-  const int NP = group_np(a.N);
-  const size_t dbl = evid_rows(a) * NP + (NP > 16 ? 2 * (size_t)NP * NP : 0) + 2 * kGroupWaves * 64;
-  return dbl * sizeof(double);
-}
+size_t chain_stream_soft_lds_bytes(const StreamSoftArgs& a) { return soft_lds_bytes(a); }
 
 int chain_stream_soft_prepare(const StreamSoftArgs& a) {
   if (!sstr_shape_ok(a)) return kLaunchRefused;
