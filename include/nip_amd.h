@@ -43,9 +43,9 @@ extern "C" {
 #define NIPAMD_STATUS_ZERO_MASS    1u  /* some m2 == 0: ll = -DBL_MAX (src/nip.c:1471-1473) */
 #define NIPAMD_STATUS_BAD_LUCK     2u  /* e_step's m1<=0 || m2<=0 || ll>0 (src/nip.c:1827-1854);
                                           nipamd_estep sets ZERO_MASS|BAD_LUCK */
-#define NIPAMD_STATUS_BAD_EVIDENCE 4u  /* nipamd_fb_soft / nipamd_filter_soft / nipamd_stream_push_soft: a
-                                          likelihood weight that is negative, NaN or infinite (set besides
-                                          ZERO_MASS) */
+#define NIPAMD_STATUS_BAD_EVIDENCE 4u  /* nipamd_fb_soft / nipamd_filter_soft / nipamd_mlss_soft /
+                                          nipamd_stream_push_soft: a likelihood weight that is negative, NaN
+                                          or infinite (set besides ZERO_MASS) */
 
 typedef struct nipamd_model nipamd_model;
 
@@ -660,6 +660,48 @@ int nipamd_filter_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, cons
                             const double* lik, int n_soft, const int* soft_vars,
                             int B, int T, int n_query, const int* query,
                             double* post, double* ll, uint32_t* status);
+
+/*
+ * The most likely state sequence under soft evidence: nipamd_mlss with the
+ * step evidence of nipamd_fb_soft -- the marginal MAP of the interface sequence
+ * with the children summed out, a soft child under its likelihood vector,
+ *
+ *   e_t[y]     = prod_hard E_k[o_{k,t}][y]  prod_soft sum_o w_{k,t}[o] E_k[o][y]
+ *   delta_0[y] = (sum_x pi[x] A[x][y]) e_0[y]
+ *   delta_t[y] = (max_x delta_{t-1}[x] A[x][y]) e_t[y]     psi_t[y] = the LOWEST x attaining the max
+ *
+ * so that posterior rows one model wrote for a variable (nipamd_fb, query =
+ * that variable) decode the model above it without being cut down to their
+ * arg-max first.  d_obs, d_lik, the accepted weights and their layout are
+ * nipamd_fb_soft's; d_path, d_logp and d_status nipamd_mlss's.  Each vector is
+ * used at the scale of its largest weight, an exact power of two whose
+ * exponent goes into logp: d_logp = ln max_y delta_{T-1}[y] with the weights as
+ * given, and multiplying a step's vector by 2^k adds k ln 2 to it and changes
+ * not one bit of any comparison or of the path, for any finite non-negative
+ * vector with a positive entry, denormals to DBL_MAX.  All ones means "not
+ * observed", a one-hot vector is a hard observation.  A sequence without mass
+ * -- an all-zero vector, no overlap with the states the chain can be in -- gets
+ * NIPAMD_STATUS_ZERO_MASS, logp = -DBL_MAX and -1 in every path entry; a weight
+ * that is negative, NaN or infinite leaves its step without evidence and adds
+ * NIPAMD_STATUS_BAD_EVIDENCE.  A sequence's outputs depend on that sequence's
+ * inputs alone, bit for bit.
+ *
+ * Scope (decided on the host, before the device is touched;
+ * NIPAMD_ERROR_UNSUPPORTED with the condition in nipamd_last_error): that of
+ * nipamd_fb_soft for the model and the evidence columns; nipamd_mlss's for the
+ * query -- exactly the interface, every variable of it once, in any order;
+ * evidence tables that fit a CU's LDS.  NULL pointers: NIP_ERROR_NULLPOINTER.
+ * B < 1, T < 1, a variable index out of range: NIP_ERROR_INVALID_ARGUMENT.
+ */
+int nipamd_mlss_soft(nipamd_model* m, const int32_t* d_obs, int n_obs, const int* obs_vars,
+                     const double* d_lik, int n_soft, const int* soft_vars,
+                     int B, int T, int n_query, const int* query,
+                     int32_t* d_path, double* d_logp, uint32_t* d_status, void* stream);
+/* Host-buffer form (copies in and out and synchronises). */
+int nipamd_mlss_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, const int* obs_vars,
+                          const double* lik, int n_soft, const int* soft_vars,
+                          int B, int T, int n_query, const int* query,
+                          int32_t* path, double* logp, uint32_t* status);
 
 /*
  * Online inference under soft evidence: a stream whose steps bring likelihood

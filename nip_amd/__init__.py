@@ -23,6 +23,7 @@ __all__ = ["NipError", "Model", "parse_model", "lib", "forward_backward_inferenc
            "most_likely_states", "most_likely_states_host", "Stream",
            "forward_backward_inference_soft", "forward_inference_soft",
            "forward_backward_inference_soft_host", "forward_inference_soft_host",
+           "most_likely_states_soft", "most_likely_states_soft_host",
            "e_step", "estep_partial", "estep_finalize", "em_learn", "read_timeseries",
            "write_uncertainseries", "write_model", "em_learn_series", "LIB_PATH"]
 
@@ -74,6 +75,7 @@ EXPORTS = [
     "nipamd_stream_push_host", "nipamd_stream_flush_host",
     "nipamd_fb_soft", "nipamd_filter_soft", "nipamd_fb_soft_host", "nipamd_filter_soft_host",
     "nipamd_stream_open_soft", "nipamd_stream_push_soft", "nipamd_stream_push_soft_host",
+    "nipamd_mlss_soft", "nipamd_mlss_soft_host",
 ]
 
 
@@ -119,6 +121,8 @@ def lib():
         L.nipamd_filter_soft.argtypes = L.nipamd_fb_soft.argtypes
         L.nipamd_fb_soft_host.argtypes = L.nipamd_fb_soft.argtypes[:-1]
         L.nipamd_filter_soft_host.argtypes = L.nipamd_fb_soft_host.argtypes
+        L.nipamd_mlss_soft.argtypes = L.nipamd_fb_soft.argtypes
+        L.nipamd_mlss_soft_host.argtypes = L.nipamd_fb_soft_host.argtypes
         L.nipamd_stream_open.argtypes = [vp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.POINTER(vp)]
         L.nipamd_stream_push.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
         L.nipamd_stream_flush.argtypes = [vp, vp, vp, vp, vp]
@@ -439,13 +443,13 @@ def forward_inference_host(model: Model, obs, obs_vars, query):
     return _run_host(lib().nipamd_filter_host, model, obs, obs_vars, query)
 
 
-def _run_soft_device(fn, model, obs, obs_vars, lik, soft_vars, query, post, ll, status, stream):
-    """obs (None when obs_vars is empty and lik is given) and lik (None when
-    soft_vars is empty) must be exactly what the kernel reads through their raw
-    pointers; B and T come from whichever is given."""
+def _soft_device_inputs(model, obs, obs_vars, lik, soft_vars):
+    """The device inputs of a soft-evidence call, checked: obs (None when
+    obs_vars is empty and lik is given) and lik (None when soft_vars is empty)
+    must be exactly what the kernel reads through their raw pointers; B and T
+    come from whichever is given.  Returns (obs, B, T, device)."""
     import torch
     W = sum(model.card(v) for v in soft_vars)
-    width = sum(model.card(v) for v in query)
     shape = None
     if lik is not None or len(soft_vars):
         if (not torch.is_tensor(lik) or lik.dtype != torch.float64 or not lik.is_cuda or not lik.is_contiguous()
@@ -467,20 +471,13 @@ def _run_soft_device(fn, model, obs, obs_vars, lik, soft_vars, query, post, ll, 
                            "obs must be a contiguous int32 CUDA tensor of shape (B, T, %d), B and T and the device "
                            "as lik's" % len(obs_vars))
         shape, dev = (int(obs.shape[0]), int(obs.shape[1])), obs.device
-    B, T = shape
-    post = _out_buf(post, (B, T, width), torch.float64, dev, "post")
-    ll = _out_buf(ll, (B,), torch.float64, dev, "ll")
-    status = _out_buf(status, (B,), torch.int32, dev, "status")
-    _check(fn(model._h, C.c_void_p(obs.data_ptr() if len(obs_vars) else 0), len(obs_vars), _ints(obs_vars),
-              C.c_void_p(lik.data_ptr() if len(soft_vars) else 0), len(soft_vars), _ints(soft_vars), B, T,
-              len(query), _ints(query), C.c_void_p(post.data_ptr()), C.c_void_p(ll.data_ptr()),
-              C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
-    return post, ll, status
+    return obs, shape[0], shape[1], dev
 
 
-def _run_soft_host(fn, model, obs, obs_vars, lik, soft_vars, query):
+def _soft_host_inputs(model, obs, obs_vars, lik, soft_vars):
+    """The host inputs of a soft-evidence call as contiguous arrays, checked.
+    Returns (obs, lik, B, T)."""
     W = sum(model.card(v) for v in soft_vars)
-    width = sum(model.card(v) for v in query)
     B = T = None
     if lik is not None:
         lik = np.ascontiguousarray(np.asarray(lik, np.float64))
@@ -499,13 +496,36 @@ def _run_soft_host(fn, model, obs, obs_vars, lik, soft_vars, query):
         B, T = obs.shape[:2]
     elif len(obs_vars) or B is None:
         raise NipError(NIP_ERROR_INVALID_ARGUMENT, "obs may be None only when obs_vars is empty and lik is given")
+    return obs, lik, B, T
+
+
+def _soft_call(fn, model, obs, obs_vars, lik, soft_vars, query, B, T, out, ll, status, *stream):
+    """fn over checked inputs and outputs: torch tensors on the device (then
+    with the stream), numpy arrays on the host."""
+    ptr = (lambda a: C.c_void_p(a.data_ptr())) if stream else (lambda a: a.ctypes.data_as(C.c_void_p))
+    _check(fn(model._h, ptr(obs) if obs is not None and len(obs_vars) else None, len(obs_vars), _ints(obs_vars),
+              ptr(lik) if lik is not None and len(soft_vars) else None, len(soft_vars), _ints(soft_vars), B, T,
+              len(query), _ints(query), ptr(out), ptr(ll), ptr(status), *stream))
+
+
+def _run_soft_device(fn, model, obs, obs_vars, lik, soft_vars, query, post, ll, status, stream):
+    import torch
+    obs, B, T, dev = _soft_device_inputs(model, obs, obs_vars, lik, soft_vars)
+    width = sum(model.card(v) for v in query)
+    post = _out_buf(post, (B, T, width), torch.float64, dev, "post")
+    ll = _out_buf(ll, (B,), torch.float64, dev, "ll")
+    status = _out_buf(status, (B,), torch.int32, dev, "status")
+    _soft_call(fn, model, obs, obs_vars, lik, soft_vars, query, B, T, post, ll, status, _stream_ptr(stream))
+    return post, ll, status
+
+
+def _run_soft_host(fn, model, obs, obs_vars, lik, soft_vars, query):
+    obs, lik, B, T = _soft_host_inputs(model, obs, obs_vars, lik, soft_vars)
+    width = sum(model.card(v) for v in query)
     post = np.zeros((B, T, width))
     ll = np.zeros(B)
     status = np.zeros(B, np.uint32)
-    _check(fn(model._h, obs.ctypes.data_as(C.c_void_p) if obs is not None and len(obs_vars) else None, len(obs_vars),
-              _ints(obs_vars), lik.ctypes.data_as(C.c_void_p) if lik is not None and len(soft_vars) else None,
-              len(soft_vars), _ints(soft_vars), B, T, len(query), _ints(query), post.ctypes.data_as(C.c_void_p),
-              ll.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+    _soft_call(fn, model, obs, obs_vars, lik, soft_vars, query, B, T, post, ll, status)
     return post, ll, status
 
 
@@ -591,6 +611,43 @@ def most_likely_states_host(model: Model, obs, obs_vars, query):
     _check(lib().nipamd_mlss_host(model._h, obs.ctypes.data_as(C.c_void_p), nobs, _ints(obs_vars),
                                   B, T, len(query), _ints(query), path.ctypes.data_as(C.c_void_p),
                                   logp.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+    return path, logp, status
+
+
+def most_likely_states_soft(model: Model, obs, obs_vars, lik, soft_vars, query, path=None, logp=None, status=None,
+                            stream=None):
+    """most_likely_states under hard and soft (likelihood) evidence on the GPU
+    (nipamd_mlss_soft): the most likely sequence of the interface with every
+    child summed out, a soft child under its likelihood vector -- so the
+    posterior rows of one model decode the next without being cut down to
+    their arg-max.
+
+    obs, obs_vars, lik, soft_vars: as forward_backward_inference_soft takes
+    them (lik float64 [B, T, sum card(soft_vars)], obs None when obs_vars is
+    empty).  query: the model's interface variable(s), all of them.  Returns
+    (path [B, T, len(query)] int32, logp [B] float64, status [B] int32), CUDA
+    tensors, computed asynchronously on ``stream``.  logp is that of the
+    weights as given: scaling a step's vector by 2^k adds k ln 2 and moves no
+    path.  A sequence without mass has STATUS_ZERO_MASS (with
+    STATUS_BAD_EVIDENCE after a negative, NaN or infinite weight), logp
+    -DBL_MAX and a path of -1."""
+    import torch
+    obs, B, T, dev = _soft_device_inputs(model, obs, obs_vars, lik, soft_vars)
+    path = _out_buf(path, (B, T, len(query)), torch.int32, dev, "path")
+    logp = _out_buf(logp, (B,), torch.float64, dev, "logp")
+    status = _out_buf(status, (B,), torch.int32, dev, "status")
+    _soft_call(lib().nipamd_mlss_soft, model, obs, obs_vars, lik, soft_vars, query, B, T, path, logp, status,
+               _stream_ptr(stream))
+    return path, logp, status
+
+
+def most_likely_states_soft_host(model: Model, obs, obs_vars, lik, soft_vars, query):
+    """most_likely_states_soft from host numpy buffers (PCIe-inclusive, synchronous)."""
+    obs, lik, B, T = _soft_host_inputs(model, obs, obs_vars, lik, soft_vars)
+    path = np.zeros((B, T, len(query)), np.int32)
+    logp = np.zeros(B)
+    status = np.zeros(B, np.uint32)
+    _soft_call(lib().nipamd_mlss_soft_host, model, obs, obs_vars, lik, soft_vars, query, B, T, path, logp, status)
     return path, logp, status
 
 

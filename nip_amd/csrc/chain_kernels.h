@@ -354,6 +354,26 @@ size_t chain_stream_soft_lds_bytes(const StreamSoftArgs& a);
 int chain_stream_soft_prepare(const StreamSoftArgs& a);
 int chain_stream_soft_launch(const StreamSoftArgs& a, hipStream_t stream);
 
+// most likely interface state sequence under soft evidence (viterbi_soft.hip,
+// chain_viterbi_soft_kernel): chain_viterbi_kernel's recursion, back-pointers
+// and path over SoftArgs' evidence columns -- 0 .. nhard - 1 hard, col[k] their
+// column in obs; nhard .. ncol - 1 soft, col[k] where their M[k] weights start
+// in a row of lik.  Every soft vector is used at the scale of its largest
+// weight and the exponents taken out go to logp, so logp is that of the
+// weights as given.  A weight that is negative, NaN or infinite leaves its
+// step without evidence: path -1, logp = -DBL_MAX, status 1 | kSoftBadEvidence.
+// Scratch: chain_viterbi_scratch_bytes.
+struct ViterbiSoftArgs : ViterbiArgs {
+  int nhard;             // hard columns (the first ones)
+  const double* lik;     // double [B][T][W] likelihood vectors, or nullptr (nhard == ncol)
+  long lik_bstride;      // elements between sequences
+  int lik_tstride;       // elements between time steps (W)
+};
+size_t chain_viterbi_soft_lds_bytes(const ViterbiSoftArgs& a);
+// the dynamic-LDS limit of the kernel that serves a (ensure_dyn_lds): 0, or a refusal / failure
+int chain_viterbi_soft_prepare(const ViterbiSoftArgs& a);
+int chain_viterbi_soft_launch(const ViterbiSoftArgs& a, hipStream_t stream);
+
 // generate_data (generate.hip): one sampling step per variable, in sampling
 // order.  In the first slice the conditional row of step i starts at
 // tab[off0 + idx], idx = sum_c value(ctx[c]) * stride[c] (in elements) with

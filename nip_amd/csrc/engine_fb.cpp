@@ -343,17 +343,21 @@ int fb_host_impl(nipamd_model* mm, const int32_t* obs, int n_obs, const int* obs
                    });
 }
 
+}  // namespace
+
 // Sequences per chain_viterbi_kernel launch: the back-pointer scratch of a
 // launch stays within kMlssScratch (8 bytes per sequence and step at N <= 16:
 // a config-4 shard, 131072 x 1024, is one launch of exactly this size), and a
 // longer batch runs as consecutive launches over the same scratch.  A multiple
 // of 16, so every launch but the last fills its blocks.
-constexpr size_t kMlssScratch = (size_t)1 << 30;
-long mlss_chunk(int N, int T) {
+long nipamd::eng::mlss_chunk(int N, int T) {
+  constexpr size_t kMlssScratch = (size_t)1 << 30;
   const size_t per16 = nipamd::chain_viterbi_scratch_bytes(N, 16, T);
   const long c = (long)(kMlssScratch / per16) * 16;
   return c < 16 ? 16 : c;
 }
+
+namespace {
 
 // mlss: the verdict on a request -- the arguments, then the scope -- decided on
 // the host before anything touches the device.  obs / path: the caller's
@@ -365,24 +369,7 @@ int mlss_check(nipamd_model* mm, const void* obs, int n_obs, const int* obs_vars
                                B <= 0 || T <= 0, "bad arguments", n_obs, obs_vars, n_query, query))
     return rc;
   if (int rc = chain_scope(mm, "mlss", "the most likely state sequence", "")) return rc;
-  const auto& P = mm->m.chain;
-  // the variables of interest are the interface, all of it and nothing else
-  bool is_if = true;
-  if (!P.joint) {
-    is_if = n_query == 1 && query[0] == P.v_cur;
-    a.nq = 1; a.qstride[0] = 1; a.qcard[0] = P.N;
-  } else {
-    if ((int)P.jcur.size() > nipamd::kViterbiMaxQuery)
-      return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the joint interface has " + std::to_string(P.jcur.size()) +
-                                                " variables; the path holds at most " +
-                                                std::to_string(nipamd::kViterbiMaxQuery) + " columns");
-    int width = 0;
-    is_if = n_query == (int)P.jcur.size() && interface_digits(mm, n_query, query, a.qstride, a.qcard, &width);
-    a.nq = n_query;
-  }
-  if (!is_if)
-    return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: the query is not exactly the interface (every outgoing-interface "
-                                          "variable of the slice once, and no other variable)");
+  if (int rc = interface_query("mlss", mm, n_query, query, &a.nq, a.qstride, a.qcard)) return rc;
   std::string why;
   if (!route_request(mm, n_obs, obs_vars, 0, nullptr, r, why)) return fail(NIPAMD_ERROR_UNSUPPORTED, "mlss: " + why);
   return 0;

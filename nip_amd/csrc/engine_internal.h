@@ -176,7 +176,14 @@ int check_var_lists(const std::string& what, const nipamd_model* mm, bool null, 
                     const std::string& bad_msg, int n_obs, const int* obs_vars, int n_query, const int* query);
 int chain_scope(const nipamd_model* mm, const std::string& what, const char* subject, const char* no_plan);
 bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int* qstride, int* qcard, int* width);
-// the verdicts soft evidence and the streams share, and the columns' roles (a: SoftArgs or StreamSoftArgs)
+// mlss's query rule: exactly the interface; the path's columns
+int interface_query(const std::string& what, const nipamd_model* mm, int n_query, const int* query, int* nq,
+                    int* qstride, int* qcard);
+// the verdicts soft evidence and the streams share, and the columns' roles: the evidence columns alone
+// (a: ViterbiSoftArgs), and with the rows' query (a: SoftArgs or StreamSoftArgs)
+template <typename A>
+int soft_evidence_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan,
+                          int n_obs, const int* obs_vars, int n_soft, const int* soft_vars, A& a, Route& r);
 template <typename A>
 int soft_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan, int n_obs,
                  const int* obs_vars, int n_soft, const int* soft_vars, int n_query, const int* query, A& a, Route& r,
@@ -194,6 +201,9 @@ int estep_rows(const ChainPlan& P);
 bool chain_map_supported(const Model& m);
 bool estep_wide_plan(const Model& m);
 bool has_chain_estep(const Model& m);
+
+// ---- engine_fb.cpp: sequences per chain_viterbi_kernel / chain_viterbi_soft_kernel launch
+long mlss_chunk(int N, int T);
 
 // Interface-chain kernel for a route, in order of preference; each kernel
 // stages the block's observation codes in LDS, so a long sequence may not fit

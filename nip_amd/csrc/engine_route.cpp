@@ -106,15 +106,42 @@ bool interface_digits(const nipamd_model* mm, int n_query, const int* query, int
   return true;
 }
 
-// What soft_check and stream_check decide after check_var_lists, in this order:
-// the soft variables, chain_scope (subject, no_plan), a variable both hard and
-// soft, the route of the hard columns followed by the soft ones, the query.
-// Fills r and of a: N, ncol, nhard, M, col (a soft column's: where its weights
-// start in a row of lik), lik_tstride, the query digits, post_tstride = *width.
+// mlss's query rule (nipamd_mlss, nipamd_mlss_soft): the variables of interest
+// are the interface, all of it and nothing else.  Fills the path's columns:
+// *nq, qstride / qcard [*nq] (a single interface variable: one column).
+int interface_query(const std::string& what, const nipamd_model* mm, int n_query, const int* query, int* nq,
+                    int* qstride, int* qcard) {
+  const auto& P = mm->m.chain;
+  bool is_if = true;
+  if (!P.joint) {
+    is_if = n_query == 1 && query[0] == P.v_cur;
+    *nq = 1; qstride[0] = 1; qcard[0] = P.N;
+  } else {
+    if ((int)P.jcur.size() > nipamd::kViterbiMaxQuery)
+      return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": the joint interface has " + std::to_string(P.jcur.size()) +
+                                                " variables; the path holds at most " +
+                                                std::to_string(nipamd::kViterbiMaxQuery) + " columns");
+    int width = 0;
+    is_if = n_query == (int)P.jcur.size() && interface_digits(mm, n_query, query, qstride, qcard, &width);
+    *nq = n_query;
+  }
+  if (!is_if)
+    return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": the query is not exactly the interface (every outgoing-interface "
+                                              "variable of the slice once, and no other variable)");
+  return 0;
+}
+
+// What soft_check, stream_check and mlss_soft_check decide after
+// check_var_lists, in this order: the soft variables, chain_scope (subject,
+// no_plan), a variable both hard and soft, the route of the hard columns
+// followed by the soft ones (soft_evidence_columns); then the query --
+// soft_columns: any distinct current-slice interface variables; mlss_soft_check:
+// interface_query.  soft_evidence_columns fills r and of a: N, ncol, nhard, M,
+// col (a soft column's: where its weights start in a row of lik), lik_tstride;
+// soft_columns the query digits and post_tstride = *width besides.
 template <typename A>
-int soft_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan, int n_obs,
-                 const int* obs_vars, int n_soft, const int* soft_vars, int n_query, const int* query, A& a, Route& r,
-                 int* width) {
+int soft_evidence_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan,
+                          int n_obs, const int* obs_vars, int n_soft, const int* soft_vars, A& a, Route& r) {
   for (int i = 0; i < n_soft; i++)
     if (soft_vars[i] < 0 || soft_vars[i] >= (int)mm->m.vars.size())
       return fail(NIP_ERROR_INVALID_ARGUMENT, what + ": bad soft-evidence variable");
@@ -129,6 +156,25 @@ int soft_columns(const std::string& what, nipamd_model* mm, const char* subject,
   std::string why;
   if (!route_request(mm, (int)all.size(), all.data(), 0, nullptr, r, why))
     return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": " + why);
+  a.N = P.N;
+  a.ncol = r.ncol; a.nhard = n_obs;
+  a.lik_tstride = 0;
+  for (int i = 0; i < r.ncol; i++) {
+    a.M[i] = P.emit(r.emit[i]).M;
+    a.col[i] = r.col[i];
+    if (i >= n_obs) { a.col[i] = a.lik_tstride; a.lik_tstride += a.M[i]; }
+  }
+  return 0;
+}
+template int soft_evidence_columns(const std::string&, nipamd_model*, const char*, const char*, int, const int*, int,
+                                   const int*, nipamd::ViterbiSoftArgs&, Route&);
+
+template <typename A>
+int soft_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan, int n_obs,
+                 const int* obs_vars, int n_soft, const int* soft_vars, int n_query, const int* query, A& a, Route& r,
+                 int* width) {
+  if (int rc = soft_evidence_columns(what, mm, subject, no_plan, n_obs, obs_vars, n_soft, soft_vars, a, r)) return rc;
+  const auto& P = mm->m.chain;
   bool is_if = n_query >= 1;
   if (!P.joint) {
     is_if = n_query == 1 && query[0] == P.v_cur;
@@ -143,14 +189,6 @@ int soft_columns(const std::string& what, nipamd_model* mm, const char* subject,
     return fail(NIPAMD_ERROR_UNSUPPORTED, what + ": the query is not a non-empty list of distinct current-slice "
                                               "interface variables (at most " +
                                               std::to_string(nipamd::kViterbiMaxQuery) + ")");
-  a.N = P.N;
-  a.ncol = r.ncol; a.nhard = n_obs;
-  a.lik_tstride = 0;
-  for (int i = 0; i < r.ncol; i++) {
-    a.M[i] = P.emit(r.emit[i]).M;
-    a.col[i] = r.col[i];
-    if (i >= n_obs) { a.col[i] = a.lik_tstride; a.lik_tstride += a.M[i]; }
-  }
   a.post_tstride = *width;
   return 0;
 }

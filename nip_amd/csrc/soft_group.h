@@ -4,7 +4,9 @@
 // and store, the backward step, the ll, the stream state's write-back and the
 // NH x LONG launch ladder.  The kernels' staging, lane geometry and A rows stay
 // written out in each: as routines they leave the compiler other LDS read
-// merging and register counts.  Included as chain_group.h is.
+// merging and register counts.  chain_viterbi_soft_kernel (viterbi_soft.hip)
+// takes the step's soft evidence and the ladder from here.  Included as
+// chain_group.h is.
 #pragma once
 #include <cfloat>
 
@@ -177,11 +179,14 @@ template <typename Args>
 size_t soft_lds_bytes(const Args& a) { return group_lds_doubles(a, a.N, 2) * sizeof(double); }
 
 // group_launch over NH (a.nhard) and LONG (a soft column longer than NP) besides, named by
-// kernel_of(np, nc, nh, long); one per (NH, LONG): its dynamic-LDS bookkeeping is per kernel_of
+// kernel_of(np, nc, nh, long); one per (NH, LONG): its dynamic-LDS bookkeeping is per kernel_of.
+// lds: the kernel's bytes, kSoftLds for soft_lds_bytes(a)
+constexpr size_t kSoftLds = ~(size_t)0;
 template <typename Args, typename KernelOf>
-int soft_group_launch(const Args& a, bool launch, hipStream_t stream, KernelOf kernel_of) {
+int soft_group_launch(const Args& a, bool launch, hipStream_t stream, KernelOf kernel_of, size_t lds = kSoftLds) {
+  if (lds == kSoftLds) lds = soft_lds_bytes(a);
   auto variant = [&](auto nh, auto lng) {
-    return group_launch(a, soft_lds_bytes(a), launch, stream, [kernel_of](auto np, auto nc) {
+    return group_launch(a, lds, launch, stream, [kernel_of](auto np, auto nc) {
       constexpr int NC = decltype(nc)::value, NH = decltype(nh)::value < NC ? decltype(nh)::value : NC;
       return kernel_of(np, nc, std::integral_constant<int, NH>{},
                        std::integral_constant<bool, decltype(lng)::value && NH < NC>{});
