@@ -704,6 +704,62 @@ int nipamd_mlss_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, const 
                           int32_t* path, double* logp, uint32_t* status);
 
 /*
+ * The e_step under soft evidence: the expected counts of nipamd_estep with the
+ * step evidence of nipamd_fb_soft, so that a model is trained on likelihood
+ * vectors -- the posterior rows of the model below it, a classifier's scores --
+ * and not on their arg-max.  The reference has no e_step over uncertain
+ * series; the definition is this library's.  Per sequence, every step
+ * normalised on its own (alpha^_{-1} = the prior, Z_t the step's normaliser):
+ *
+ *   K[x][y]   += alpha^_{t-1}[x] e_t[y] beta_t[y] / Z_t        (the xi sums, without the transition factor)
+ *   P0[x]      = prior[x] (A (e_0 o beta_0))[x] / Z_0
+ *   H_k[o][y] += gamma_t[y] [o = o_{k,t}]                      child k observed hard; a missing or
+ *                                                              out-of-range code in its own row, as nipamd_estep
+ *   H_k[o][y] += gamma_t[y] w[o] E_k[o][y] / sum_o' w[o'] E_k[o'][y]      child k observed soft: its
+ *                                                              posterior given y and the vector (0 where the sum is 0)
+ *   a child that no column names: gamma_t to its "missing" row
+ *
+ * d_obs, d_lik, the accepted weights and their layout are nipamd_fb_soft's, and
+ * d_ll is nipamd_fb_soft's ll of the same inputs (the same recursion; the last
+ * bit may differ).  n_soft == 0 is allowed (hard columns only).  All ones is the missing observation, a one-hot vector the
+ * hard one; multiplying a step's vector by 2^j changes no bit of the partial
+ * and adds j ln 2 to the ll.  A sequence without mass gets
+ * NIPAMD_STATUS_ZERO_MASS | NIPAMD_STATUS_BAD_LUCK (as nipamd_estep), ll =
+ * -DBL_MAX and contributes nothing to the counts; a weight that is negative,
+ * NaN or infinite adds NIPAMD_STATUS_BAD_EVIDENCE.  The reference's verdict on
+ * a leading run of missing observations (nipamd_estep_prefix_first_bad) and its
+ * rejection of ll > 0 are NOT applied: there is no reference behaviour for
+ * soft series, and weights above 1 make a positive ll legitimate.  d_ll and
+ * d_status may be NULL.
+ *
+ * d_partial: nipamd_estep_partial_size(m) doubles, a wide-chain-slab partial:
+ * nipamd_estep_finalize finalises it, and it combines (nipamd_tree_sum) with
+ * other wide-slab partials of the model.  A sequence's contribution depends on
+ * its own inputs alone and the sum over sequences is the fixed-order tree, so
+ * power-of-two shards combine into exactly the whole batch's partial.
+ * nipamd_estep_soft: partial + finalize, d_counts (em_learn layout) +=.
+ *
+ * Scope (decided on the host, before the device is touched;
+ * NIPAMD_ERROR_UNSUPPORTED with the condition in nipamd_last_error): that of
+ * nipamd_fb_soft for the evidence columns, every one of them a leaf child (not
+ * the interface variable); a model of one interface variable of at most 64
+ * states with 1..4 leaf children and independent hidden parents (no joint
+ * interface); tables and count tables that fit a CU's LDS.  NULL pointers:
+ * NIP_ERROR_NULLPOINTER.  B < 1, T < 1, a variable index out of range:
+ * NIP_ERROR_INVALID_ARGUMENT.
+ */
+int nipamd_estep_soft_partial(nipamd_model* m, const int32_t* d_obs, int n_obs, const int* obs_vars,
+                              const double* d_lik, int n_soft, const int* soft_vars,
+                              int B, int T, double* d_partial, double* d_ll, uint32_t* d_status, void* stream);
+int nipamd_estep_soft(nipamd_model* m, const int32_t* d_obs, int n_obs, const int* obs_vars,
+                      const double* d_lik, int n_soft, const int* soft_vars,
+                      int B, int T, double* d_counts, double* d_ll, uint32_t* d_status, void* stream);
+/* Host-buffer form (copies in and out and synchronises). */
+int nipamd_estep_soft_host(nipamd_model* m, const int32_t* obs, int n_obs, const int* obs_vars,
+                           const double* lik, int n_soft, const int* soft_vars,
+                           int B, int T, double* counts, double* ll, uint32_t* status);
+
+/*
  * Online inference under soft evidence: a stream whose steps bring likelihood
  * vectors -- a classifier's per-frame scores, a noisy sensor's confusion row,
  * the rows another stream has just emitted -- as they arrive.

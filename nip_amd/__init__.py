@@ -25,6 +25,7 @@ __all__ = ["NipError", "Model", "parse_model", "lib", "forward_backward_inferenc
            "forward_backward_inference_soft_host", "forward_inference_soft_host",
            "most_likely_states_soft", "most_likely_states_soft_host",
            "e_step", "estep_partial", "estep_finalize", "em_learn", "read_timeseries",
+           "e_step_soft", "estep_partial_soft", "e_step_soft_host", "em_learn_soft",
            "write_uncertainseries", "write_model", "em_learn_series", "LIB_PATH"]
 
 LIB_PATH = os.environ.get("NIPAMD_LIB", _build.LIB)
@@ -76,6 +77,7 @@ EXPORTS = [
     "nipamd_fb_soft", "nipamd_filter_soft", "nipamd_fb_soft_host", "nipamd_filter_soft_host",
     "nipamd_stream_open_soft", "nipamd_stream_push_soft", "nipamd_stream_push_soft_host",
     "nipamd_mlss_soft", "nipamd_mlss_soft_host",
+    "nipamd_estep_soft_partial", "nipamd_estep_soft", "nipamd_estep_soft_host",
 ]
 
 
@@ -123,6 +125,10 @@ def lib():
         L.nipamd_filter_soft_host.argtypes = L.nipamd_fb_soft_host.argtypes
         L.nipamd_mlss_soft.argtypes = L.nipamd_fb_soft.argtypes
         L.nipamd_mlss_soft_host.argtypes = L.nipamd_fb_soft_host.argtypes
+        L.nipamd_estep_soft_partial.argtypes = [vp, vp, C.c_int, ip, vp, C.c_int, ip, C.c_int, C.c_int,
+                                                vp, vp, vp, vp]
+        L.nipamd_estep_soft.argtypes = L.nipamd_estep_soft_partial.argtypes
+        L.nipamd_estep_soft_host.argtypes = L.nipamd_estep_soft_partial.argtypes[:-1]
         L.nipamd_stream_open.argtypes = [vp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.POINTER(vp)]
         L.nipamd_stream_push.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
         L.nipamd_stream_flush.argtypes = [vp, vp, vp, vp, vp]
@@ -1088,4 +1094,70 @@ def e_step(model: Model, obs, obs_vars, counts=None, ll=None, status=None, strea
     return counts, ll, status
 
 
+def _estep_soft_call(fn, model, obs, obs_vars, lik, soft_vars, B, T, out, ll, status, *stream):
+    """_soft_call without a query: fn over checked inputs and outputs."""
+    ptr = (lambda a: C.c_void_p(a.data_ptr())) if stream else (lambda a: a.ctypes.data_as(C.c_void_p))
+    _check(fn(model._h, ptr(obs) if obs is not None and len(obs_vars) else None, len(obs_vars), _ints(obs_vars),
+              ptr(lik) if lik is not None and len(soft_vars) else None, len(soft_vars), _ints(soft_vars), B, T,
+              ptr(out), ptr(ll), ptr(status), *stream))
+
+
+def estep_partial_soft(model: Model, obs, obs_vars, lik, soft_vars, partial=None, ll=None, status=None, stream=None):
+    """First half of the batched e_step under soft evidence
+    (nipamd_estep_soft_partial): the fixed-order tree sum of the per-sequence
+    count slabs.  obs, lik and the accepted weights as
+    forward_backward_inference_soft.  Returns (partial [partial_size] float64,
+    ll [B], status [B]) on the GPU; the partial is a wide-chain-slab partial,
+    which estep_finalize finalises and tree_sum combines with others."""
+    import torch
+    obs, B, T, dev = _soft_device_inputs(model, obs, obs_vars, lik, soft_vars)
+    S = lib().nipamd_estep_partial_size(model._h)
+    if S < 0:
+        raise NipError(NIPAMD_ERROR_UNSUPPORTED, "model has no GPU e_step plan")
+    partial = _out_buf(partial, (S,), torch.float64, dev, "partial")
+    ll = _out_buf(ll, (B,), torch.float64, dev, "ll")
+    status = _out_buf(status, (B,), torch.int32, dev, "status")
+    _estep_soft_call(lib().nipamd_estep_soft_partial, model, obs, obs_vars, lik, soft_vars, B, T, partial, ll, status,
+                     _stream_ptr(stream))
+    return partial, ll, status
+
+
+def e_step_soft(model: Model, obs, obs_vars, lik, soft_vars, counts=None, ll=None, status=None, stream=None):
+    """Batched e_step under hard and soft (likelihood) evidence on the GPU
+    (nipamd_estep_soft): the expected counts of e_step with a soft child's
+    count row shared out as the child's posterior given its vector.  All ones
+    is the missing observation, a one-hot vector the hard one.  counts: CUDA
+    float64 [param_size] accumulated into (default: ones, the em_learn
+    pseudo-counts).  Returns (counts, ll [B], status [B]); a sequence without
+    mass has STATUS_ZERO_MASS | STATUS_BAD_LUCK and adds nothing to the counts.
+    The reference's verdicts on leading missing runs and on ll > 0 do not apply."""
+    import torch
+    obs, B, T, dev = _soft_device_inputs(model, obs, obs_vars, lik, soft_vars)
+    if counts is None:
+        counts = torch.ones((model.param_size(),), dtype=torch.float64, device=dev)
+    counts = _out_buf(counts, (model.param_size(),), torch.float64, dev, "counts")
+    ll = _out_buf(ll, (B,), torch.float64, dev, "ll")
+    status = _out_buf(status, (B,), torch.int32, dev, "status")
+    _estep_soft_call(lib().nipamd_estep_soft, model, obs, obs_vars, lik, soft_vars, B, T, counts, ll, status,
+                     _stream_ptr(stream))
+    return counts, ll, status
+
+
+def e_step_soft_host(model: Model, obs, obs_vars, lik, soft_vars, counts=None):
+    """e_step_soft from host numpy buffers (PCIe-inclusive, synchronous).
+    counts: float64 [param_size] accumulated into (default: ones)."""
+    obs, lik, B, T = _soft_host_inputs(model, obs, obs_vars, lik, soft_vars)
+    P = model.param_size()
+    if counts is None:
+        counts = np.ones(P)
+    if not (isinstance(counts, np.ndarray) and counts.dtype == np.float64 and counts.shape == (P,)
+            and counts.flags.c_contiguous):
+        raise NipError(NIP_ERROR_INVALID_ARGUMENT, "counts must be a contiguous float64 array of shape (%d,)" % P)
+    ll = np.zeros(B)
+    status = np.zeros(B, np.uint32)
+    _estep_soft_call(lib().nipamd_estep_soft_host, model, obs, obs_vars, lik, soft_vars, B, T, counts, ll, status)
+    return counts, ll, status
+
+
 from .em import em_learn  # noqa: E402
+from .em_soft import em_learn_soft  # noqa: E402

@@ -374,6 +374,27 @@ size_t chain_viterbi_soft_lds_bytes(const ViterbiSoftArgs& a);
 int chain_viterbi_soft_prepare(const ViterbiSoftArgs& a);
 int chain_viterbi_soft_launch(const ViterbiSoftArgs& a, hipStream_t stream);
 
+// e_step under soft evidence (estep_soft.hip, chain_estep_soft_kernel):
+// chain_soft_kernel's forward pass and scratch over SoftArgs' evidence columns
+// (post, nq and filter unused), whose backward pass accumulates the e_step's
+// three sums instead of writing rows: one wide slab row (estep_wide_slab: K
+// [NP][NP], H [R][NP], P0 [NP]) per sequence, all zero for a sequence without
+// mass.  A hard column's step goes to row code_of of its child, a soft column's
+// to the child's state rows as the child's posterior given y and the vector;
+// status: 1 | 2 for a sequence without mass, kSoftBadEvidence besides.
+struct EstepSoftArgs : SoftArgs {
+  double* slab;          // [B][slab_size]
+  int slab_size;
+  int R;                 // count-table rows: sum over the plan's children of M_k + 2
+  int hrow[4];           // first count-table row of each evidence column's child
+  int n_unobs;           // plan children that no column names
+  int urow[4];           // their "missing" rows
+};
+size_t chain_estep_soft_lds_bytes(const EstepSoftArgs& a);
+// the dynamic-LDS limit of the kernel that serves a (ensure_dyn_lds): 0, or a refusal / failure
+int chain_estep_soft_prepare(const EstepSoftArgs& a);
+int chain_estep_soft_launch(const EstepSoftArgs& a, hipStream_t stream);
+
 // generate_data (generate.hip): one sampling step per variable, in sampling
 // order.  In the first slice the conditional row of step i starts at
 // tab[off0 + idx], idx = sum_c value(ctx[c]) * stride[c] (in elements) with

@@ -14,6 +14,7 @@
 // the finalize instead of being summed silently.
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 
 #include "engine_internal.h"
 
@@ -688,6 +689,22 @@ int map_finalize(const DevState* d, const double* d_partial, double* d_counts, v
 }
 
 }  // namespace
+
+// ---- what engine_estep_soft.cpp takes of the above (engine_internal.h)
+namespace nipamd::eng {
+
+int wide_slab_chunks(nipamd_model* mm, int S, long chunk, size_t scratch, long B, double* d_partial, hipStream_t st,
+                     const std::function<int()>& prepare,
+                     const std::function<int(long, long, double*)>& launch) {
+  const SlabRun run{S, chunk, 1, scratch, {0.0, 0.0, 1.0}};
+  return run_slab_chunks(mm, run, B, d_partial, st, prepare, launch);
+}
+
+long estep_pow2_chunk(size_t per_seq, size_t budget, long lo, long hi) { return pow2_chunk(per_seq, budget, lo, hi); }
+
+long estep_chunk_limit() { return kEstepChunk; }
+
+}  // namespace nipamd::eng
 
 extern "C" {
 

@@ -5,12 +5,14 @@
 //   engine_route.cpp  request routing and kernel choice (host data only)
 //   engine_fb.cpp     fb / filter / mlss launch sites
 //   engine_estep.cpp  e_step partial routes, CSR maps, finalize
+//   engine_estep_soft.cpp  the e_step under soft evidence
 //   engine_diag.cpp   diagnostics builds: phase-stamp buffers and reports
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <deque>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -201,6 +203,14 @@ int estep_rows(const ChainPlan& P);
 bool chain_map_supported(const Model& m);
 bool estep_wide_plan(const Model& m);
 bool has_chain_estep(const Model& m);
+
+// ---- engine_estep.cpp, for the e_step under soft evidence (engine_estep_soft.cpp): the wide route's
+// partial (tag (0, 0, 1)) from one slab row [S] per sequence -- run_slab_chunks with per_row = 1 --
+// pow2_chunk, and the most sequences of a launch
+int wide_slab_chunks(nipamd_model* mm, int S, long chunk, size_t scratch, long B, double* d_partial, hipStream_t st,
+                     const std::function<int()>& prepare, const std::function<int(long, long, double*)>& launch);
+long estep_pow2_chunk(size_t per_seq, size_t budget, long lo, long hi);
+long estep_chunk_limit();
 
 // ---- engine_fb.cpp: sequences per chain_viterbi_kernel / chain_viterbi_soft_kernel launch
 long mlss_chunk(int N, int T);

@@ -168,6 +168,8 @@ int soft_evidence_columns(const std::string& what, nipamd_model* mm, const char*
 }
 template int soft_evidence_columns(const std::string&, nipamd_model*, const char*, const char*, int, const int*, int,
                                    const int*, nipamd::ViterbiSoftArgs&, Route&);
+template int soft_evidence_columns(const std::string&, nipamd_model*, const char*, const char*, int, const int*, int,
+                                   const int*, nipamd::EstepSoftArgs&, Route&);
 
 template <typename A>
 int soft_columns(const std::string& what, nipamd_model* mm, const char* subject, const char* no_plan, int n_obs,
